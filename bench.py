@@ -16,12 +16,32 @@ GPU, fp16 storage / fp32 accumulate.  A step = one batch through the captured hi
 all_gather of the exchange record when N>1.  Weak scaling: 8 images per GPU, image i of the
 global batch on rank i % N.
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` for the dominant kernel family
-(conv family, per-launch numbers from HIP events around every op of an eager replay on the
-launch stream; `frac` = that single-stream figure, `frac_end_to_end` = the same FLOPs over the
-wall clock of the timed loop with all batches in flight), `cpu_baseline` (the CPU oracle, bounded
-sample, rank 0 at N=1 only) and `secondary` = BASELINE config 3 (`mp_det_res50`: ResNet-50 + GL-fusion
-plug-in + FPN + MPHead at 8 x 800 x 1344) measured the same way in the same run.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times ONE window of exactly --steps
+steps (`ms_per_step` = that window / --steps) and prints the line; nothing else is measured.
+
+--full adds what the headline does not need: the timed window repeated (--windows, default 9; the
+line then reports the median window), `roofline` for the dominant kernel family (conv family,
+per-launch numbers from HIP events around every op of an eager replay on the launch stream; `frac` =
+that single-stream figure, `frac_end_to_end` = the same FLOPs over the wall clock of the timed loop
+with all batches in flight), `cpu_baseline` (the CPU oracle, bounded sample, rank 0 at N=1 only),
+`secondary` = BASELINE config 3 (`mp_det_res50`: ResNet-50 + GL-fusion plug-in + FPN + MPHead at
+8 x 800 x 1344) measured the same way in the same run, the `f32_strict` and `config2` legs and
+`tertiary` (the two-stage pipeline).  --op-table needs --full.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed (rank 0): the
+detections [n, max_det, 7] (rows past each image's count zeroed), the per-image counts and, for the
+YOLOX detectors, the decoded predictions [n, A, 5 + nc], as DIR/<name>.npy in float32.  Inputs and
+weights are seeded, and the kernel variants come from a fixed table (bench_tuning.json, below), so two
+runs with the same arguments compute the same outputs.
+
+Kernel selection: the autotuner times the variants of every conv problem and keeps the fastest, so
+near-ties fall differently from run to run; different variants (fused chain or not, tile shape) round
+differently, and this random-weight net amplifies that to a few % of the logits at 800 x 1344 -- enough
+to move boxes across the NMS threshold.  The benchmark therefore installs bench_tuning.json (the tuner's
+own table for every workload here, recorded on an MI355X with GLSDET_TUNE_CACHE) before it builds
+anything: the tuner finds every key and measures nothing.  --retune (or a GLSDET_TUNE_CACHE of one's
+own) measures afresh instead, as tuning studies need; `kernel_selection` in the line says which was used
+and how many entries the run added (problems the tuner had to measure, or loaded from that cache).
 """
 import argparse
 import glob
@@ -37,6 +57,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+KERNEL_SELECTION = os.path.join(ROOT, "bench_tuning.json")     # {dtype: {json(tuner key): variant}}, Engine's cache format
 
 PEAK_F16_TFLOPS = 2500.0      # MI355X dense fp16 MFMA (MI355X_MICROARCH.md, chip-level parameters)
 PEAK_F32_TFLOPS = 157.3       # exact-f32 MFMA (same table)
@@ -256,6 +277,18 @@ def _torch_decode(outs, H, W):
     return flat.contiguous()
 
 
+def _std64(t):
+    """Unbiased std in float64 on the host (numpy's pairwise sum): the same value on every device and thread count,
+    unlike a device reduction, whose order follows the launch geometry."""
+    return float(np.std(t.detach().cpu().numpy().astype(np.float64), ddof=1))
+
+
+def bench_input(bs, H, W, rank):
+    """The benchmark batch: N(0, 1) drawn on the host from a generator seeded with the rank, then copied to the device
+    (a device generator's stream depends on the launch geometry, i.e. on the device it runs on)."""
+    return torch.randn(bs, 3, H, W, generator=torch.Generator().manual_seed(rank))
+
+
 def calibrate_yolox_head(sd, kind, img, args, dev):
     """Make the random-init head behave like a trained one for the post-processing load (weights only; the
     timed path is untouched; SURVEY 8d "dense mode"):
@@ -281,7 +314,7 @@ def calibrate_yolox_head(sd, kind, img, args, dev):
     for k, o in enumerate(outs):
         b = sd["head.reg_preds.%d.bias" % k].to(o.device).view(1, 4, 1, 1)
         r = o[:, :4] - b
-        scales.append((0.5 / float(r[:, :2].std().clamp(min=1e-6)), 0.35 / float(r[:, 2:].std().clamp(min=1e-6))))
+        scales.append((0.5 / max(_std64(r[:, :2]), 1e-6), 0.35 / max(_std64(r[:, 2:]), 1e-6)))
         sd["head.obj_preds.%d.bias" % k] = sd["head.obj_preds.%d.bias" % k] + shift
     eng = Engine("f32", dev)
     n, A = outs[0].shape[0], sum(o.shape[2] * o.shape[3] for o in outs)
@@ -315,17 +348,69 @@ def calibrate_yolox_head(sd, kind, img, args, dev):
 
 
 # --------------------------------------------------------------------------------------------- one workload
-def run_workload(args, workload, rank, world, dev, with_cpu_baseline, nsteps=None, nwindows=None, leg=""):
-    """Build, calibrate, time (warmup + exactly --steps steps between barriers) and profile per op ONE workload.
-    -> (result dict, elapsed seconds) on every rank."""
+def install_kernel_selection(path=KERNEL_SELECTION):
+    """Put the recorded tuning table into the engine's shared table (all dtypes) -> number of entries installed."""
+    from glsdet_amd import engine
+    with open(path) as f:
+        tab = json.load(f)
+    for dt, items in tab.items():
+        engine._SHARED_TUNED.setdefault(dt, {}).update({tuple(json.loads(k)): v for k, v in items.items()})
+    return sum(len(v) for v in tab.values())
+
+
+def tuned_entries():
+    from glsdet_amd import engine
+    return sum(len(v) for v in engine._SHARED_TUNED.values())
+
+
+def dump_outputs(path, arrays, limit=63 << 20):
+    """arrays: name -> ndarray, written as path/<name>.npy in float32.  Above `limit` bytes in all, the biggest arrays
+    are cut to a fixed, seeded sample of their rows (same rows in every run of the same shape); 63 MB leaves room for
+    the .npy headers under 64 MB."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for k in sorted(arrays, key=lambda k: -arrays[k].nbytes):
+        if total <= limit:
+            break
+        a = arrays[k]
+        rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+        keep = max(1, int(max(0, limit - (total - a.nbytes)) // (rows.shape[1] * 4 + 8)))     # a row + its float64 index
+        idx = np.sort(np.random.default_rng(0).choice(len(rows), size=min(keep, len(rows)), replace=False))
+        arrays[k] = np.ascontiguousarray(rows[idx])
+        arrays[k + "_sample_rows"] = idx.astype(np.float64)
+        total += arrays[k].nbytes + arrays[k + "_sample_rows"].nbytes - a.nbytes
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(arrays)
+
+
+def step_outputs(ci, bs, exch=None):
+    """What one step of the timed path hands its caller, read from plan instance `ci` (host copies)."""
+    nb = ci.nb if hasattr(ci, "nb") else ci.nmsb
+    count = nb["count"][:bs].cpu().numpy()
+    dets = nb["dets"].cpu().numpy()
+    for i in range(bs):
+        dets[i, count[i]:] = 0.0
+    out = {"detections": dets, "detection_counts": count.astype(np.float32)}
+    if getattr(ci, "decoded", None) is not None:
+        out["decoded"] = ci.decoded.cpu().numpy()
+    if exch is not None and exch.out is not None:
+        out["gathered"] = exch.out.cpu().numpy()         # the exchange record every rank receives (N > 1)
+    return out
+
+
+def run_workload(args, workload, rank, world, dev, with_cpu_baseline, nsteps=None, nwindows=None, leg="", dump=None):
+    """Build, calibrate, time (warmup + exactly --steps steps between barriers, --windows times) ONE workload; with --full
+    also profile it per op (roofline).  dump: directory for the last timed step's outputs (rank 0), or None.
+    -> result dict on every rank."""
     import torch.distributed as dist
     from glsdet_amd.dist import DetectionExchange, ranks_agree
 
     nsteps = args.steps if nsteps is None else nsteps
     nwindows = args.windows if nwindows is None else nwindows
     kind, tag, H, W, bs = WORKLOADS[workload]
-    gen = torch.Generator(device=dev).manual_seed(rank)
-    img = torch.randn(bs, 3, H, W, generator=gen, device=dev)
+    img = bench_input(bs, H, W, rank).to(dev)
     nstreams = 1 if args.no_graph else max(1, args.streams)
     calib = {}
     if kind in RESDET:
@@ -437,11 +522,56 @@ def run_workload(args, workload, rank, world, dev, with_cpu_baseline, nsteps=Non
         assert read_back[1] == nsteps, "every timed batch must have delivered its counts to the host"
         windows.append(el)
     elapsed = float(np.median(windows))
+    if dump and rank == 0:
+        last = (turn[0] - 1) % nstreams      # the plan instance that ran the last timed step
+        dump_outputs(dump, step_outputs(cs[last], bs, exch[last] if exch else None))
     dets = det.collect(c)                    # also checks the NMS capacity/overflow flags
     if kind in RESDET:
         dets = [d[0] for d in dets]
+    wall_ms = elapsed / nsteps * 1e3
+    roofline = per_op_roofline(args, workload, kind, H, W, bs, c, dev, wall_ms, nstreams, rank, leg) if args.full else None
 
-    # ---- per-op timing of the same plan (eager replay, HIP events on the launch stream)
+    if kind in RESDET:      # stage-1 counters: [image][level] pairs above the threshold; NMS input = per-level top-k merged
+        nl = len(c.cls)
+        cand_counts = c.nb["ws"][: 4 * bs * nl].view(torch.int32).view(bs, nl).sum(1).cpu().tolist()
+        nms_in = [int(min(v, post["nms_pre"] * nl)) for v in cand_counts]
+        unclamped = c.nb["count"][bs:2 * bs].cpu().tolist()
+    else:
+        cand_counts = [int(v) for v in c.nmsb["ws"][: 4 * bs].view(torch.int32).cpu().tolist()]
+        nms_in = cand_counts
+        unclamped = c.nmsb["count"][bs:2 * bs].cpu().tolist()
+    suppressed = 1.0 - float(sum(unclamped)) / max(1, sum(nms_in))
+    n_img = bs * world * nsteps
+    res = {"workload": workload, "value": round(n_img / elapsed, 2), "unit": "img/s",
+           "ms_per_step": round(wall_ms, 4), "steps": nsteps,
+           "windows": {"n": len(windows), "steps_each": nsteps, "statistic": "median",
+                       "ms_per_step_min": round(min(windows) / nsteps * 1e3, 4), "ms_per_step_max": round(max(windows) / nsteps * 1e3, 4)},
+           "config": {"workload": workload, "detector": DETECTOR_NAME[kind],
+                      "input": [bs, 3, H, W], "images_per_gpu": bs, "global_batch": bs * world, "num_classes": 10,
+                      "post": post, "head_calibration": calib, "hip_graph": not args.no_graph,
+                      "batches_in_flight": nstreams, "settle_seconds_untimed": args.settle,
+                      "input_from_host_each_step": bool(args.from_host),
+                      "detections_per_image_rank0": [int(len(d)) for d in dets],
+                      "candidates_per_image_rank0": cand_counts,
+                      "suppressed_frac": round(suppressed, 4),
+                      "detections_read_back_in_timed_loop_rank0": read_back[0],
+                      "parallelism": "image-sharded dp%d, one all_gather of detections per step" % world,
+                      "exchange": ({"rows_per_image": post["exchange_cap"],
+                                    "images_truncated_by_the_cap_rank0": int(sum(1 for v in unclamped if v > post["exchange_cap"]))}
+                                   if world > 1 else None)}}
+    if roofline is not None:
+        res["roofline"] = roofline
+    if with_cpu_baseline:
+        res["cpu_baseline"] = resdet_cpu_baseline(sd, kind, H, W, post["score_thr"], post["max_per_img"]) \
+            if kind in RESDET else cpu_baseline(sd, kind, bs, H, W, args.conf, args.nms)
+    del cs, c, det, exch
+    torch.cuda.empty_cache()
+    return res
+
+
+def per_op_roofline(args, workload, kind, H, W, bs, c, dev, wall_ms, nstreams, rank, leg):
+    """--full: per-op timing of the timed plan (eager replay, HIP events on the launch stream) -> the `roofline` object;
+    writes --op-table on rank 0."""
     ops = c.plan.ops()
     st = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(st):
@@ -460,7 +590,6 @@ def run_workload(args, workload, rank, world, dev, with_cpu_baseline, nsteps=Non
     all_ms = float(ms.sum())
     peak = PEAK_F16_TFLOPS if args.dtype == "f16" else PEAK_F32_TFLOPS
     achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-    wall_ms = elapsed / nsteps * 1e3
     e2e = 2.0 * (alg_conv_gmac + alg_mm_gmac) * 1e9 * bs / (wall_ms * 1e-3) / 1e12
     # the same two figures on the FLOPs the launched kernels execute (weight composition / re-association remove algorithmic
     # work: `frac` then says how fast the JOB is, `frac_executed` how busy the MFMA pipe is)
@@ -503,42 +632,7 @@ def run_workload(args, workload, rank, world, dev, with_cpu_baseline, nsteps=Non
                 f.write("%d\t%d\t%.4f\t%.3f\t%.1f\t%.2f\t%.0f\t%s\n" % (
                     i, o["kind"], t, o["flops"] / 1e9, o["flops"] / max(t, 1e-6) / 1e9, o["bytes"] / 1e6,
                     o["bytes"] / max(t, 1e-6) / 1e6, o["name"]))
-
-    if kind in RESDET:      # stage-1 counters: [image][level] pairs above the threshold; NMS input = per-level top-k merged
-        nl = len(c.cls)
-        cand_counts = c.nb["ws"][: 4 * bs * nl].view(torch.int32).view(bs, nl).sum(1).cpu().tolist()
-        nms_in = [int(min(v, post["nms_pre"] * nl)) for v in cand_counts]
-        unclamped = c.nb["count"][bs:2 * bs].cpu().tolist()
-    else:
-        cand_counts = [int(v) for v in c.nmsb["ws"][: 4 * bs].view(torch.int32).cpu().tolist()]
-        nms_in = cand_counts
-        unclamped = c.nmsb["count"][bs:2 * bs].cpu().tolist()
-    suppressed = 1.0 - float(sum(unclamped)) / max(1, sum(nms_in))
-    n_img = bs * world * nsteps
-    res = {"workload": workload, "value": round(n_img / elapsed, 2), "unit": "img/s",
-           "ms_per_step": round(wall_ms, 4), "steps": nsteps,
-           "windows": {"n": len(windows), "steps_each": nsteps, "statistic": "median",
-                       "ms_per_step_min": round(min(windows) / nsteps * 1e3, 4), "ms_per_step_max": round(max(windows) / nsteps * 1e3, 4)},
-           "config": {"workload": workload, "detector": DETECTOR_NAME[kind],
-                      "input": [bs, 3, H, W], "images_per_gpu": bs, "global_batch": bs * world, "num_classes": 10,
-                      "post": post, "head_calibration": calib, "hip_graph": not args.no_graph,
-                      "batches_in_flight": nstreams, "settle_seconds_untimed": args.settle,
-                      "input_from_host_each_step": bool(args.from_host),
-                      "detections_per_image_rank0": [int(len(d)) for d in dets],
-                      "candidates_per_image_rank0": cand_counts,
-                      "suppressed_frac": round(suppressed, 4),
-                      "detections_read_back_in_timed_loop_rank0": read_back[0],
-                      "parallelism": "image-sharded dp%d, one all_gather of detections per step" % world,
-                      "exchange": ({"rows_per_image": post["exchange_cap"],
-                                    "images_truncated_by_the_cap_rank0": int(sum(1 for v in unclamped if v > post["exchange_cap"]))}
-                                   if world > 1 else None)},
-           "roofline": roofline}
-    if with_cpu_baseline:
-        res["cpu_baseline"] = resdet_cpu_baseline(sd, kind, H, W, post["score_thr"], post["max_per_img"]) \
-            if kind in RESDET else cpu_baseline(sd, kind, bs, H, W, args.conf, args.nms)
-    del cs, c, det, exch
-    torch.cuda.empty_cache()
-    return res
+    return roofline
 
 
 def run_two_stage(args, rank, world, dev):
@@ -731,7 +825,14 @@ def main():
     ap.add_argument("--exchange-cap", type=int, default=0,
                     help="rows per image of the all_gather record (N>1); 0 = the detector's own cap (max_det / max_per_img): "
                          "nothing a rank keeps is cut by the exchange")
-    ap.add_argument("--windows", type=int, default=9, help="timed windows of exactly --steps steps; the median is reported")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of exactly --steps steps; the median is reported (default 1, with --full 9)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: repeated windows, per-op timing (roofline, "
+                         "--op-table), the CPU baseline, the secondary / f32_strict / config2 / tertiary legs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (detections, counts, decoded predictions) "
+                         "as DIR/<name>.npy in float32 (rank 0)")
     ap.add_argument("--no-legs", action="store_true", help="skip the extra legs (f32_strict, BASELINE config 2 at 640x640)")
     ap.add_argument("--nms", type=float, default=0.65)
     ap.add_argument("--no-graph", action="store_true")
@@ -746,6 +847,9 @@ def main():
     ap.add_argument("--settle", type=float, default=1.5,
                     help="seconds of untimed steps before the warmup (clock / power ramp of a cold box); 0 = none")
     ap.add_argument("--no-autotune", action="store_true")
+    ap.add_argument("--retune", action="store_true",
+                    help="measure the kernel variants in this run instead of installing bench_tuning.json (run-dependent "
+                         "choices; also the case when GLSDET_TUNE_CACHE is set)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the BASELINE config-3 leg (`secondary`)")
     ap.add_argument("--no-tertiary", action="store_true", help="skip the BASELINE config-5 leg (`tertiary`: two-stage UFPMP pipeline)")
@@ -753,6 +857,10 @@ def main():
     ap.add_argument("--hang-dump", type=int, default=0, metavar="SECONDS",
                     help="dump every thread's stack to stderr and exit if the run is still going after SECONDS (debugging aid)")
     args = ap.parse_args()
+    if args.op_table and not args.full:
+        ap.error("--op-table needs --full (the per-op timing runs only there)")
+    if args.windows is None:
+        args.windows = 9 if args.full else 1
     if args.hang_dump and ("WORLD_SIZE" in os.environ or args.gpus == 1):        # the ranks, not the launcher
         import faulthandler
         faulthandler.dump_traceback_later(args.hang_dump, exit=True)
@@ -783,15 +891,23 @@ def main():
         if rank == 0:
             print("[bench %6.1fs] %s" % (time.perf_counter() - t_start, what), file=sys.stderr, flush=True)
     t_start = time.perf_counter()
-    base = world == 1 and not args.no_cpu_baseline
+    if args.no_autotune:
+        selection = {"source": "size heuristic (--no-autotune)"}
+    elif args.retune or os.environ.get("GLSDET_TUNE_CACHE"):
+        selection = {"source": "measured in this run" + (" (GLSDET_TUNE_CACHE)" if os.environ.get("GLSDET_TUNE_CACHE") else "")}
+    else:
+        selection = {"source": os.path.basename(KERNEL_SELECTION), "entries": install_kernel_selection()}
+    entries0 = tuned_entries()
+    base = world == 1 and args.full and not args.no_cpu_baseline
     progress("workload %s on %d rank(s)" % (args.workload, world))
-    main_res = run_workload(args, args.workload, rank, world, dev, base)
+    main_res = run_workload(args, args.workload, rank, world, dev, base, dump=args.dump_outputs or None)
     second = None
-    if not args.no_secondary and args.workload != SECONDARY:
+    if args.full and not args.no_secondary and args.workload != SECONDARY:
         progress("secondary workload %s" % SECONDARY)
         second = run_workload(args, SECONDARY, rank, world, dev, base)
     legs = {}
-    if not args.no_legs and not args.no_secondary and args.workload == "yolox_s_glfusion_1344x800_bs8" and args.dtype == "f16":
+    if args.full and not args.no_legs and not args.no_secondary and args.workload == "yolox_s_glfusion_1344x800_bs8" and \
+            args.dtype == "f16":
         import copy
         progress("leg f32_strict (the mode that meets north_star's 1e-4 / 1e-3: exact-f32 MFMA)")
         a32 = copy.copy(args)
@@ -804,7 +920,8 @@ def main():
         legs["config2"] = dict(run_workload(args, "yolox_s_glfusion_640x640_bs8", rank, world, dev, False, nwindows=min(args.windows, 5)),
                                dtype=args.dtype, n_gpus=world, note="BASELINE.json configs[1] at its named shape")
     third = None
-    if not args.no_tertiary and not args.no_secondary and args.workload == "yolox_s_glfusion_1344x800_bs8" and not args.no_graph:
+    if args.full and not args.no_tertiary and not args.no_secondary and args.workload == "yolox_s_glfusion_1344x800_bs8" and \
+            not args.no_graph:
         progress("tertiary workload ufpmp_two_stage_540x1024")
         third = run_two_stage(args, rank, world, dev)
     progress("done")
@@ -815,8 +932,11 @@ def main():
             "warmup": args.warmup, "ms_per_step": main_res["ms_per_step"], "windows": main_res["windows"],
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": args.dtype, "data": "synthetic",
-            "config": main_res["config"], "roofline": main_res["roofline"],
+            "config": main_res["config"],
+            "kernel_selection": dict(selection, entries_added_in_this_run=tuned_entries() - entries0),
         }
+        if "roofline" in main_res:
+            line["roofline"] = main_res["roofline"]
         if "cpu_baseline" in main_res:
             line["cpu_baseline"] = main_res["cpu_baseline"]
         if second is not None:

@@ -6,7 +6,7 @@ mkdir -p $out
 export GLSDET_TUNE_CACHE=$out/tune.json
 run() {
   tag=$1; shift
-  GLSDET_SKIP_OPS="$1" python bench.py --no-secondary --no-cpu-baseline --steps 100 --warmup 10 --max-det 30000 > $out/$tag.json 2> $out/$tag.err
+  GLSDET_SKIP_OPS="$1" python bench.py --full --no-secondary --no-cpu-baseline --steps 100 --warmup 10 --max-det 30000 > $out/$tag.json 2> $out/$tag.err
   python - "$tag" "$out/$tag.json" <<'PY'
 import json, sys
 try:

@@ -3,7 +3,7 @@
 out=gpurun_out/${1:-tune_diff}; mkdir -p $out
 for i in 1 2 3; do
   export GLSDET_TUNE_CACHE=$PWD/$out/tune$i.json; rm -f $GLSDET_TUNE_CACHE
-  timeout -k 10 250 python bench.py --no-secondary --no-cpu-baseline --windows 5 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('tuning $i', d['value'], d['ms_per_step'], d['roofline']['launches_per_step'])"
+  timeout -k 10 250 python bench.py --full --no-secondary --no-cpu-baseline --windows 5 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('tuning $i', d['value'], d['ms_per_step'], d['roofline']['launches_per_step'])"
   # the same table again (no tuning): run-to-run spread of ONE selection
   timeout -k 10 250 python bench.py --no-secondary --no-cpu-baseline --windows 5 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('   replayed', d['value'], d['ms_per_step'])"
 done
