@@ -10,7 +10,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libglsdet_hip.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 CAPTURE_LOCK = threading.RLock()        # hipGraph captures are serialised across host threads
 
 F16, F32 = 0, 1
@@ -44,7 +44,15 @@ class ConvChain(C.Structure):
                 ("act2", C.c_int32), ("c0", C.c_int32), ("cin2", C.c_int32), ("flags", C.c_int32)]
 
 
+class CspDesc(C.Structure):
+    _fields_ = [("x", View), ("y", View)] + \
+               [(k + q, C.c_void_p) for q in ("12", "m1", "m2", "3") for k in ("w", "scale", "bias")] + \
+               [("act", C.c_int32), ("shortcut", C.c_int32)]
+
+
 _SIGS = {
+    "glsdet_csp_fused": (C.c_int, [C.POINTER(CspDesc), C.c_int32, C.c_void_p]),
+    "glsdet_csp_fused_tune": (C.c_int, [C.POINTER(CspDesc), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "glsdet_conv2d_chain": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvChain), C.c_void_p]),
     "glsdet_conv2d_chain_tune": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvChain), C.c_void_p, C.POINTER(C.c_int32),
                                            C.POINTER(C.c_float)]),

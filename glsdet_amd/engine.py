@@ -363,6 +363,93 @@ class Engine:
                                        "differ": float((a != b).float().mean())})
         return ok
 
+    # ---- a whole CSPLayer (64 -> 64, hidden 32, one Bottleneck) as ONE launch (glsdet_csp_fused)
+    def _tmp(self, n: int, h: int, w: int, c: int, sn: Optional[int] = None, sh: Optional[int] = None,
+             sw: Optional[int] = None) -> TView:
+        """a view on a buffer of its own that is freed with it (tuner comparisons, shadow checks)"""
+        sw = c if sw is None else sw
+        sh = w * sw if sh is None else sh
+        sn = h * sh if sn is None else sn
+        buf = torch.zeros(ceil_to(n * sn * _ESIZE[self.dt], 256), dtype=torch.uint8, device=self.device)
+        return TView(buf, 0, n, h, w, c, sn, sh, sw, self.dt)
+
+    def _csp_desc(self, x: TView, out: TView, packs, shortcut: bool) -> "_lib.CspDesc":
+        d = _lib.CspDesc()
+        d.x, d.y = x.as_c(), out.as_c()
+        for q, pk in zip(("12", "m1", "m2", "3"), packs):
+            setattr(d, "w" + q, pk[0].data_ptr())
+            setattr(d, "scale" + q, pk[1].data_ptr())
+            setattr(d, "bias" + q, pk[2].data_ptr())
+        d.act, d.shortcut = ACT["silu"], 1 if shortcut else 0
+        return d
+
+    def _csp_unfused(self, x: TView, packs, shortcut: bool, out: TView, launch) -> None:
+        """the four launches glsdet_csp_fused replaces, on buffers of their own; launch(x, pack, pad, out, res)"""
+        cat = self._tmp(x.n, x.h, x.w, 64)
+        t = self._tmp(x.n, x.h, x.w, 32)
+        main = cat.channels(0, 32)
+        launch(x, packs[0], 0, cat, None)
+        launch(main, packs[1], 0, t, None)
+        launch(t, packs[2], 1, main, main if shortcut else None)
+        launch(cat, packs[3], 0, out, None)
+
+    def csp_fused_wins(self, xg, og, packs, shortcut: bool) -> bool:
+        """Would Engine.csp_fused take the layer?  xg / og = (n, h, w, c, sn, sh, sw) of its input / output view (the input
+        may not exist yet: the caller decides BEFORE it emits the layer's producer); packs = the packed convs conv1|conv2,
+        m.0.conv1, m.0.conv2, conv3.  Records no op.  Without autotune: wherever the entry point accepts the operands.  With
+        autotune the fused launch must beat the four tuned launches it replaces (each timed by glsdet_conv2d_tune on
+        buffers of its own; only the key ("csp1", ...) is stored)."""
+        if self.dt != F16 or xg[3] != 64 or og[3] != 64 or tuple(xg[:3]) != tuple(og[:3]) or len(packs) != 4 or \
+                [(pk[3], pk[4], pk[5]) for pk in packs] != [(64, 1, 1), (32, 1, 1), (32, 3, 3), (64, 1, 1)]:
+            return False
+        if not self.autotune:
+            return True
+        key = ("csp1",) + tuple(int(v) for v in xg) + tuple(int(v) for v in og) + (bool(shortcut), int(self.dt))
+        if key not in self._tuned:
+            x, out = self._tmp(*xg), self._tmp(*og)
+            st = _stream_ptr(self.stream)
+            d = self._csp_desc(x, out, packs, shortcut)
+            best, us = C.c_int32(0), C.c_float(0)
+            hint = best.value if self.lib.glsdet_csp_fused_tune(C.byref(d), st, C.byref(best), C.byref(us)) == 0 else -1
+            if hint >= 0:
+                sep = []
+
+                def tune(xi, pk, pad, o, res):
+                    dd = ConvDesc()
+                    dd.x, dd.y = xi.as_c(), o.as_c()
+                    dd.res = res.as_c() if res is not None else View()
+                    dd.w, dd.scale, dd.bias = pk[0].data_ptr(), pk[1].data_ptr(), pk[2].data_ptr()
+                    dd.R, dd.S, dd.stride, dd.pad, dd.act, dd.tile_hint = pk[4], pk[5], 1, pad, ACT["silu"], 0
+                    b, u = C.c_int32(0), C.c_float(0)
+                    sep.append(u.value if self.lib.glsdet_conv2d_tune(C.byref(dd), st, C.byref(b), C.byref(u)) == 0 else None)
+
+                self._csp_unfused(x, packs, shortcut, out, tune)
+                if None not in sep and us.value > 0.97 * sum(sep) + _fuse_credit_us():
+                    hint = -1
+            self._tuned[key] = hint
+            self._tune_dirty = True
+        return self._tuned[key] >= 0
+
+    def csp_fused(self, x: TView, packs, shortcut: bool, out: TView) -> bool:
+        """The CSPLayer x -> out in ONE launch (glsdet_csp_fused; packs as for csp_fused_wins): bit-identical to the four
+        launches.  Returns False, having launched nothing, when the entry point refuses the operands."""
+        hint = 0
+        if self.autotune:
+            key = ("csp1", x.n, x.h, x.w, x.c, x.sn, x.sh, x.sw, out.n, out.h, out.w, out.c, out.sn, out.sh, out.sw,
+                   bool(shortcut), int(self.dt))
+            hint = max(self._tuned.get(key, 0), 0)
+        d = self._csp_desc(x, out, packs, shortcut)
+        ok = self.lib.glsdet_csp_fused(C.byref(d), hint, _stream_ptr(self.stream)) == 0
+        if ok and self.shadow is not None:      # against the four-launch form on the same operands: bit for bit
+            ref = self._tmp(out.n, out.h, out.w, out.c)
+            self._csp_unfused(x, packs, shortcut, ref,
+                              lambda xi, pk, pad, o, res: self.conv(xi, pk, 1, pad, "silu", out=o, res=res, tile_hint=1))
+            a, b = out.to_nchw(), ref.to_nchw()
+            self.shadow["log"].append({"shape": (x.n, out.h, out.w, 64, 64, 3, 3), "scale": float(a.abs().max()),
+                                       "err": float((a - b).abs().max()), "nan": bool(torch.isnan(a).any()),
+                                       "differ": float((a != b).float().mean())})
+        return ok
+
     def conv_multi(self, xs: Sequence[TView], packs, stride: int, pad: int, act: str,
                    outs: Optional[Sequence[Optional[TView]]] = None, ress: Optional[Sequence[Optional[TView]]] = None,
                    out_dtype: Optional[int] = None, tile_hint: int = 0) -> List[TView]:

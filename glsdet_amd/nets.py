@@ -194,9 +194,52 @@ class NetBuilder:
             x = self.cba(dp, dx, 2)
         self.cba(list(prefixes), x, out=dst)
 
-    def csp(self, p: str, x: Optional[TView], shortcut: bool, out: Optional[TView] = None, down=None) -> TView:
+    def _csp_whole(self, p: str, x: Optional[TView], shortcut: bool, out: Optional[TView], down, hid: int, n: int):
+        """The whole CSPLayer as ONE launch (Engine.csp_fused: 64 -> 64 channels, hidden 32, one Bottleneck, fp16) where that
+        form applies and the engine takes it.  The decision is made before anything is emitted: with `down` it decides whether
+        the stride-2 producer is emitted on its own (into the contiguous tensor cba() would give it) or left to the chained
+        forms of _csp_entry.  GLSDET_NO_CSP_FUSION=1 (read here, at plan build) keeps the other lowerings.
+        -> (y, x, down): y the output, or None with x / down for the other lowerings (nothing of the layer has been emitted
+        then, at most its producer)."""
+        if self.trace is not None or self.e.dt == F32 or hid != 32 or n != 1 or os.environ.get("GLSDET_NO_CSP_FUSION"):
+            return None, x, down
+        names = [p + ".conv1", p + ".conv2", p + ".m.0.conv1", p + ".m.0.conv2", p + ".conv3"]
+        if any(self.is_depthwise(q) for q in names) or self.sd[names[3] + ".conv.weight"].shape[-1] != 3 or \
+                self.sd[names[0] + ".conv.weight"].shape[1] != 64 or self.conv_out_channels(names[4]) != 64:
+            return None, x, down
+        if x is None:
+            dx = down[1]
+            dn, dh, dw = dx.n, (dx.h + 2 - 3) // 2 + 1, (dx.w + 2 - 3) // 2 + 1
+            xg = (dn, dh, dw, 64, dh * dw * 64, dw * 64, 64)
+        else:
+            dn, dh, dw = x.n, x.h, x.w
+            xg = (x.n, x.h, x.w, x.c, x.sn, x.sh, x.sw)
+        og = (dn, dh, dw, 64, dh * dw * 64, dw * 64, 64) if out is None else (out.n, out.h, out.w, out.c, out.sn, out.sh, out.sw)
+        packs = [self._pack(names[0] + "+" + names[1], [self._bn_part(names[0]), self._bn_part(names[1])], 64),
+                 self._pack(names[2], [self._bn_part(names[2])], 32), self._pack(names[3], [self._bn_part(names[3])], 32),
+                 self._pack(names[4], [self._bn_part(names[4])], 64)]
+        if not self.e.csp_fused_wins(xg, og, packs, shortcut):
+            return None, x, down
+        if x is None:
+            # the producer on its own, into the contiguous tensor cba() would give it.  With autotune it runs on the kernel
+            # tuned for that problem, as wherever the tuner rejects the chained form; without, on the generic kernel, which
+            # is what the chained form it replaces here runs it on (the default ring kernel sums a k step on another MFMA
+            # shape: results one ulp apart) -- so taking or not taking the whole-layer form moves no bit in either mode
+            pk = self._pack(down[0], [self._bn_part(down[0])], down[1].c)
+            x = self.e.conv(down[1], pk, 2, 1, "silu", tile_hint=0 if self.e.autotune else 1)
+            self._rec(down[0], x, 0, pk[3])
+            down = None
+        y = out if out is not None else self.e.tensor(dn, dh, dw, 64)
+        if not self.e.csp_fused(x, packs, shortcut, y):
+            return None, x, down
+        self._rec(names[4], y, 0, 64)
+        return y, x, down
+
+    def csp(self, p: str, x: Optional[TView], shortcut: bool, out: Optional[TView] = None, down=None, whole: bool = False) -> TView:
         """CSPLayer (darknet.py:66-112).  down: see _csp_entry (x is then None: the layer's input exists only inside the
-        producing launch).  Where the fused kernel applies and pays, a Bottleneck (1x1 -> 3x3 [+ x],
+        producing launch).  whole: let the layer run as ONE launch where that form exists and the engine takes it
+        (_csp_whole; off by default, so that the lowerings below stay what a direct caller gets).
+        Where the fused kernel applies and pays, a Bottleneck (1x1 -> 3x3 [+ x],
         darknet.py:61-64) is ONE launch that recomputes the 1x1 on the 3x3's halo (glsdet_bottleneck): the hidden tensor
         never reaches memory.  That form cannot run in place, so the main branch ping-pongs between two channel slots
         P | Q of one buffer [P | short | Q]; conv1|conv2 write [main | short] into [P | short] for an even number of
@@ -208,6 +251,10 @@ class NetBuilder:
         n = 0
         while self.has("%s.m.%d.conv1.conv.weight" % (p, n)):
             n += 1
+        if whole:       # the layer as one launch (opt-in: NetBuilder.darknet); bit-identical, so the choice never moves results
+            y, x, down = self._csp_whole(p, x, shortcut, out, down, hid, n)
+            if y is not None:
+                return y
         # (tracing keeps the unfused form: a trace holds EVERY stored tensor, and the fused form equals it bit for bit)
         if n and hid in (32, 64, 128) and not os.environ.get("GLSDET_NO_BNECK_FUSION") and self.trace is None and \
                 not self.is_depthwise("%s.m.0.conv2" % p) and self.sd["%s.m.0.conv2.conv.weight" % p].shape[-1] == 3:
@@ -306,18 +353,18 @@ class NetBuilder:
                 else:
                     x = self.cba(d0, x, 2)
             if att(i + 2):
-                x = self.csp("%s.%s.1" % (p, name), x, True, down=down)
+                x = self.csp("%s.%s.1" % (p, name), x, True, down=down, whole=True)
                 x = self.attention("%s.lsk%d" % (p, i + 2), x, out=homes.get(name))
             else:
-                x = self.csp("%s.%s.1" % (p, name), x, True, out=homes.get(name), down=down)
+                x = self.csp("%s.%s.1" % (p, name), x, True, out=homes.get(name), down=down, whole=True)
             f[name] = x
         x = self.cba(p + ".dark5.0", x, 2)
         x = self.spp(p + ".dark5.1", x)
         if att(5):
-            x = self.csp(p + ".dark5.2", x, False)
+            x = self.csp(p + ".dark5.2", x, False, whole=True)
             x = self.attention(p + ".lsk5", x, out=homes.get("dark5"))
         else:
-            x = self.csp(p + ".dark5.2", x, False, out=homes.get("dark5"))
+            x = self.csp(p + ".dark5.2", x, False, out=homes.get("dark5"), whole=True)
         f["dark5"] = x
         return f
 

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GLSDET_ABI_VERSION 13
+#define GLSDET_ABI_VERSION 14
 
 enum { GLSDET_F16 = 0, GLSDET_F32 = 1 };
 enum { GLSDET_ACT_NONE = 0, GLSDET_ACT_SILU = 1, GLSDET_ACT_RELU = 2, GLSDET_ACT_LRELU = 3,
@@ -147,6 +147,31 @@ int     glsdet_conv2d_chain_tune(const glsdet_conv_desc* d, const glsdet_conv_ch
 int     glsdet_bottleneck(const glsdet_conv_desc* c1, const glsdet_conv_desc* c2, int32_t hint, void* stream);
 int     glsdet_bottleneck_tune(const glsdet_conv_desc* c1, const glsdet_conv_desc* c2, void* stream, int32_t* best_hint,
                                float* best_us);
+/* A whole CSPLayer in ONE launch (drone/models/base/darknet.py:66-112, `x_1 = self.conv1(x); x_2 = self.conv2(x);
+ * x_1 = self.m(x_1); x = torch.cat((x_1, x_2), dim=1); return self.conv3(x)` with the Bottleneck of :61-64), ABI 14:
+ *     main  = act(bn(conv1(x)))   short = act(bn(conv2(x)))         w12 = ONE packed 1x1 conv 64 -> 64, rows [conv1 | conv2]
+ *     h     = act(bn(m.0.conv1(main)))                              wm1: 1x1 32 -> 32
+ *     main' = act(bn(m.0.conv2(h))) (+ main when shortcut)          wm2: 3x3 32 -> 32, stride 1, pad 1
+ *     y     = act(bn(conv3([main' | short])))                       w3:  1x1 64 -> 64
+ * Weights / scale / bias packed as for glsdet_conv2d (cin 64, 32, 32, 64).  A workgroup keeps all 18.4 K weights resident
+ * and walks a strip of pixel tiles; main, short, h and main' live in LDS only, each rounded to fp16 exactly where the
+ * four-launch form stores it, every product in the k order of the stand-alone kernels: y equals four glsdet_conv2d bit
+ * for bit.  Limits: fp16 x and y, x.c == y.c == 64 (hidden 32, ONE Bottleneck), any n / h / w and view strides; y must
+ * not overlap x other than as a disjoint channel slice of the same pixel-interleaved buffer.  Anything else is refused
+ * with a negative code before any launch (callers fall back to the separate launches).
+ * hint 0 / 1: 8 x 16 / 4 x 16 pixel tiles.                                                                              */
+typedef struct glsdet_csp_desc {
+  glsdet_view x, y;
+  const void*  w12;  const float* scale12; const float* bias12;
+  const void*  wm1;  const float* scalem1; const float* biasm1;
+  const void*  wm2;  const float* scalem2; const float* biasm2;
+  const void*  w3;   const float* scale3;  const float* bias3;
+  int32_t act;             /* of all five BaseConvs: GLSDET_ACT_SILU (the only one compiled)      */
+  int32_t shortcut;        /* 1: main' += main (Bottleneck.use_add)                             */
+} glsdet_csp_desc;
+int     glsdet_csp_fused(const glsdet_csp_desc* d, int32_t hint, void* stream);
+/* times both tile heights on the device (synchronises; never recorded into a plan); y is written with the result */
+int     glsdet_csp_fused_tune(const glsdet_csp_desc* d, void* stream, int32_t* best_hint, float* best_us);
 /* Depthwise k x k conv + folded BN + act (`dconv` of DWConv, drone/models/base/baseConv.py:22-30;
  * mmcv DepthwiseSeparableConvModule).  Same descriptor; x.c == y.c; w = [R*S][x.c] elements of
  * x.dtype (tap-major), scale/bias fp32 [x.c]; res must be empty. */
