@@ -24,6 +24,11 @@ struct DecodeArgs {
 __device__ __forceinline__ float sigmoidf_acc(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // drone/models/core/utils_bbox.py:266-305 (mode 0) / mmdet yolox_head.py:298-308 (mode 1)
+// SIG: which score channels go through the sigmoid -- bit 0 objectness (channel 4), bit 1 the classes (5 .. 5 + nc); the
+// others are copied through as the raw logit (utils_bbox.py:36-253: decode_outputs_cls_sigmoid = 2, _no_sigmoid = 1,
+// _no_sigmoid_all = 0, _xyxy = mode 1 with 0).  A template parameter: SIG = 3 is the kernel as it was, and no
+// instantiation tests the channel index inside its class loop.
+template <int SIG>
 __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
   const long total = (long)a.n * a.A;
   const int F = 5 + a.nc;
@@ -53,7 +58,16 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
       }
       o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2;
     }
-    for (int c = 4; c < F; ++c) o[c] = sigmoidf_acc(p[c]);
+    if constexpr (SIG == 3) {
+      for (int c = 4; c < F; ++c) o[c] = sigmoidf_acc(p[c]);
+    } else {
+      o[4] = (SIG & 1) ? sigmoidf_acc(p[4]) : p[4];
+      if constexpr (SIG & 2) {
+        for (int c = 5; c < F; ++c) o[c] = sigmoidf_acc(p[c]);
+      } else {
+        for (int c = 5; c < F; ++c) o[c] = p[c];
+      }
+    }
   }
 }
 
@@ -889,11 +903,13 @@ static long nms_layout(int n, int max_cand, NmsWs* ws, char* base, bool with_mas
 
 using namespace glsdet;
 
-extern "C" int glsdet_yolox_decode(const glsdet_view* levels, int32_t n_levels, int32_t num_classes, int32_t in_h,
-                                   int32_t in_w, const int32_t* strides, int32_t mode, float* out, int64_t out_elems,
-                                   const float* scale_factors, void* stream) {
+extern "C" int glsdet_yolox_decode_ex(const glsdet_view* levels, int32_t n_levels, int32_t num_classes, int32_t in_h,
+                                      int32_t in_w, const int32_t* strides, int32_t mode, int32_t sigmoid_mask, float* out,
+                                      int64_t out_elems, const float* scale_factors, void* stream) {
   if (!levels || !out || n_levels < 1 || n_levels > GLS_MAX_LEVELS) GLS_FAIL(GLSDET_E_ARG, "yolox_decode: bad levels");
   if (num_classes < 1 || mode < 0 || mode > 1) GLS_FAIL(GLSDET_E_ARG, "yolox_decode: bad num_classes/mode");
+  if (sigmoid_mask < 0 || sigmoid_mask > 3)
+    GLS_FAIL(GLSDET_E_ARG, "yolox_decode: bad sigmoid_mask %d (bit 0 objectness, bit 1 classes)", sigmoid_mask);
   DecodeArgs a = {};
   int A = 0;
   for (int l = 0; l < n_levels; ++l) {
@@ -922,14 +938,22 @@ extern "C" int glsdet_yolox_decode(const glsdet_view* levels, int32_t n_levels, 
   op.flops = 0;
   op.bytes = (double)a.n * A * (5 + num_classes) * 8.0;
   op.name = "yolox_decode";
-  op.launch = [a](hipStream_t st) -> int {
+  op.launch = [a, sigmoid_mask](hipStream_t st) -> int {
     long g = ((long)a.n * a.A + 255) / 256;
     if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(decode_kernel, dim3((unsigned)g), dim3(256), 0, st, a);
+    void (*const kern[4])(const DecodeArgs) = {decode_kernel<0>, decode_kernel<1>, decode_kernel<2>, decode_kernel<3>};
+    hipLaunchKernelGGL(kern[sigmoid_mask], dim3((unsigned)g), dim3(256), 0, st, a);
     GLS_HIP(hipGetLastError());
     return 0;
   };
   return submit(std::move(op), stream);
+}
+
+extern "C" int glsdet_yolox_decode(const glsdet_view* levels, int32_t n_levels, int32_t num_classes, int32_t in_h,
+                                   int32_t in_w, const int32_t* strides, int32_t mode, float* out, int64_t out_elems,
+                                   const float* scale_factors, void* stream) {
+  return glsdet_yolox_decode_ex(levels, n_levels, num_classes, in_h, in_w, strides, mode, 3, out, out_elems, scale_factors,
+                                stream);
 }
 
 extern "C" int64_t glsdet_nms_workspace_bytes(int32_t n, int32_t A, int32_t max_cand) {

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import Engine, Plan, TView
+from .engine import DECODE_MODES, Engine, Plan, TView
 from .nets import build_forward
 
 
@@ -32,7 +32,8 @@ class HipDetector:
     # ------------------------------------------------------------------ compile
     def compile(self, n: int, H: int, W: int, post: Optional[dict] = None, use_graph: bool = False,
                 instance: int = 0) -> _Compiled:
-        """post: None (raw logits only) or dict(conf_thres, nms_thres, max_cand, max_det, mode, exchange_cap);
+        """post: None (raw logits only) or dict(conf_thres, nms_thres, max_cand, max_det, mode, sigmoid, exchange_cap);
+        sigmoid = the decode's sigmoid mask (bit 0 objectness, bit 1 classes; default 3 = both, see DECODE_MODES);
         exchange_cap = K appends the multi-GPU exchange record ([n, K+1, 7], Engine.pack_detections) to the plan.
         `instance` > 0 builds an independent copy (own buffers, own stream) of the same plan, so
         consecutive batches can be in flight concurrently (see run_async)."""
@@ -58,7 +59,7 @@ class HipDetector:
                 A = sum(l.h * l.w for l in c.levels)
                 c.decoded = eng.decode(c.levels, self.num_classes, H, W, mode=post.get("mode", 0),
                                        strides=[8, 16, 32] if post.get("mode", 0) == 1 else None,
-                                       scale_factors=c.scale)
+                                       scale_factors=c.scale, sigmoid=post.get("sigmoid", 3))
                 # candidate capacity per image: 4096 unless the caller asks for more (the class-segmented NMS kernels take up to
                 # 4096 candidates per image; beyond that the three-kernel path of rounds 1-2 runs as well).  More candidates
                 # than the capacity raise the status flag -> HipDetector.collect says "raise max_cand".
@@ -128,10 +129,18 @@ class HipDetector:
         self.run(c, img.to(c.img.device, torch.float32))
         return [l.to_nchw(5 + self.num_classes) for l in c.levels]
 
-    def detect(self, img: torch.Tensor, conf_thres: float, nms_thres: float, max_det: int = 1000, mode: int = 0):
-        """-> (decoded [B,A,5+nc] device tensor, list per image of ndarray(k,7) [x1,y1,x2,y2,obj,cls_conf,cls])"""
+    def detect(self, img: torch.Tensor, conf_thres: float, nms_thres: float, max_det: int = 1000, mode: int = 0,
+               decode_mode: str = "default"):
+        """-> (decoded [B,A,5+nc] device tensor, list per image of ndarray(k,7) [x1,y1,x2,y2,obj,cls_conf,cls])
+        decode_mode: the reference harness's name (drone/yolo.py:75-82) for the score channels that get a sigmoid --
+        'default' | 'obj_sigmoid' | 'no_sigmoid' | 'cls_sigmoid'; the others reach the NMS as raw logits."""
+        if decode_mode not in DECODE_MODES:
+            raise ValueError("decode_mode must be one of %s (got %r)" % (sorted(DECODE_MODES), decode_mode))
         n, _, H, W = img.shape
-        c = self.compile(n, H, W, dict(conf_thres=conf_thres, nms_thres=nms_thres, max_det=max_det, mode=mode))
+        post = dict(conf_thres=conf_thres, nms_thres=nms_thres, max_det=max_det, mode=mode)
+        if DECODE_MODES[decode_mode] != 3:          # the default keeps the plan-cache key it always had
+            post["sigmoid"] = DECODE_MODES[decode_mode]
+        c = self.compile(n, H, W, post)
         self.run(c, img.to(c.img.device, torch.float32))
         return c.decoded, self.collect(c)
 

@@ -1,12 +1,12 @@
-"""Twin of drone/models/core/utils_bbox.py (the functions the reference harness calls,
-yolo.py:143-150): same names, arguments and return values; arithmetic in libglsdet_hip."""
+"""Twin of drone/models/core/utils_bbox.py (the functions the reference harness imports and calls,
+yolo.py:12, 75-82, 143-150): same names, arguments and return values; arithmetic in libglsdet_hip."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
 from glsdet_amd._lib import F32
-from glsdet_amd.engine import Engine
+from glsdet_amd.engine import DECODE_MODES, Engine
 
 _ENG = {}
 
@@ -38,15 +38,15 @@ def yolo_correct_boxes(box_xy, box_wh, input_shape, image_shape, letterbox_image
     return boxes
 
 
-def decode_outputs(outputs, input_shape):
-    """[B,5+nc,H,W] x levels -> [B, A, 5+nc] (sigmoid on obj/cls, grid decode, normalised by
-    input (w, h)); drone/models/core/utils_bbox.py:254-306.  Unlike the reference it does not
-    mutate `outputs`."""
+def _decode(outputs, input_shape, mode, sigmoid):
+    """The one decode behind the five reference names: box format `mode` and sigmoid mask as glsdet_yolox_decode_ex
+    takes them.  `outputs` is either the RawOutputs of our own forward (its native fp32 NHWC levels are decoded in
+    place of the NCHW copies) or any list of [B,5+nc,H,W] tensors, staged to NHWC levels.  Not mutated."""
     comp = getattr(outputs, "compiled", None)
     nc = outputs[0].shape[1] - 5
     H, W = int(input_shape[0]), int(input_shape[1])
     if comp is not None:                       # native fp32 NHWC levels of our own forward
-        return comp.eng.decode(comp.levels, nc, H, W, mode=0)
+        return comp.eng.decode(comp.levels, nc, H, W, mode=mode, sigmoid=sigmoid)
     eng = _engine()
     levels = []
     for o in outputs:
@@ -55,7 +55,35 @@ def decode_outputs(outputs, input_shape):
         dst = torch.as_strided(v.buf.view(torch.float32), (n, h, w, v.c), (v.sn, v.sh, v.sw, 1))
         dst[..., :c] = o.detach().to(eng.device, torch.float32).permute(0, 2, 3, 1)
         levels.append(v)
-    return eng.decode(levels, nc, H, W, mode=0)
+    return eng.decode(levels, nc, H, W, mode=mode, sigmoid=sigmoid)
+
+
+def decode_outputs(outputs, input_shape):
+    """[B,5+nc,H,W] x levels -> [B, A, 5+nc] (sigmoid on obj/cls, grid decode, normalised by
+    input (w, h)); drone/models/core/utils_bbox.py:254-306.  Unlike the reference it does not
+    mutate `outputs`."""
+    return _decode(outputs, input_shape, 0, DECODE_MODES["default"])
+
+
+def decode_outputs_cls_sigmoid(outputs, input_shape):
+    """decode_mode 'cls_sigmoid' (utils_bbox.py:92-144): as decode_outputs, the objectness stays a raw logit."""
+    return _decode(outputs, input_shape, 0, DECODE_MODES["cls_sigmoid"])
+
+
+def decode_outputs_no_sigmoid(outputs, input_shape):
+    """decode_mode 'obj_sigmoid' (utils_bbox.py:146-198): as decode_outputs, the class channels stay raw logits."""
+    return _decode(outputs, input_shape, 0, DECODE_MODES["obj_sigmoid"])
+
+
+def decode_outputs_no_sigmoid_all(outputs, input_shape):
+    """decode_mode 'no_sigmoid' (utils_bbox.py:200-251): as decode_outputs, objectness and classes stay raw logits."""
+    return _decode(outputs, input_shape, 0, DECODE_MODES["no_sigmoid"])
+
+
+def decode_outputs_xyxy(outputs, input_shape):
+    """utils_bbox.py:36-90: corner boxes x1, y1, x2, y2 in input pixels (not normalised), stride = input_shape[0] / h
+    for both axes, objectness and classes raw logits."""
+    return _decode(outputs, input_shape, 1, 0)
 
 
 def non_max_suppression(prediction, num_classes, input_shape, image_shape, letterbox_image, conf_thres=0.5,

@@ -19,6 +19,9 @@ from ._lib import F16, F32, ACT, View, ConvChain, ConvDesc, check
 
 _TORCH_DT = {F16: torch.float16, F32: torch.float32}
 _ESIZE = {F16: 2, F32: 4}
+# `decode_mode` of the reference harness (drone/yolo.py:75-82) -> sigmoid mask of Engine.decode (bit 0 objectness, bit 1
+# classes); the one table HipDetector.detect and the drone twin's decode functions share
+DECODE_MODES = {"default": 3, "obj_sigmoid": 1, "no_sigmoid": 0, "cls_sigmoid": 2}
 
 
 def ceil_to(v: int, m: int) -> int:
@@ -799,7 +802,9 @@ class Engine:
 
     def decode(self, levels: Sequence[TView], num_classes: int, in_h: int, in_w: int,
                strides: Optional[Sequence[int]] = None, mode: int = 0, out: Optional[torch.Tensor] = None,
-               scale_factors: Optional[torch.Tensor] = None) -> torch.Tensor:
+               scale_factors: Optional[torch.Tensor] = None, sigmoid: int = 3) -> torch.Tensor:
+        """glsdet_yolox_decode_ex.  mode: box format (0 cx, cy, w, h / input size; 1 x1, y1, x2, y2 in pixels);
+        sigmoid: bit 0 objectness, bit 1 classes -- channels outside the mask stay raw logits (DECODE_MODES)."""
         A = sum(l.h * l.w for l in levels)
         n = levels[0].n
         if out is None:
@@ -811,8 +816,8 @@ class Engine:
         if scale_factors is not None:
             assert scale_factors.dtype == torch.float32 and scale_factors.is_contiguous() and scale_factors.numel() == 4 * n
             sf = scale_factors.data_ptr()
-        check(self.lib.glsdet_yolox_decode(arr, len(levels), num_classes, in_h, in_w, st, mode,
-                                           out.data_ptr(), out.numel(), sf, _stream_ptr(self.stream)), "yolox_decode")
+        check(self.lib.glsdet_yolox_decode_ex(arr, len(levels), num_classes, in_h, in_w, st, mode, int(sigmoid),
+                                              out.data_ptr(), out.numel(), sf, _stream_ptr(self.stream)), "yolox_decode")
         return out
 
     def nms_buffers(self, n: int, A: int, max_cand: int, max_det: int):

@@ -11,8 +11,9 @@ allocated by the op on the input's device, nothing synchronises.  There is no CP
         reference: BaseConv drone/models/base/baseConv.py:6-19 (+ Bottleneck add, darknet.py:61-62)
     glsdet::nonlocal_dot(x, tpg, ci, wout, bout) -> y
         Non_local_Block without its three projections: drone/models/block/non_local/Identity_Conv.py:157-173
-    glsdet::yolox_decode(levels, num_classes, in_h, in_w, mode) -> pred [N, A, 5+nc]
-        decode_outputs, drone/models/core/utils_bbox.py:254-306 (mode 1: mmdet YOLOXHead._bbox_decode)
+    glsdet::yolox_decode(levels, num_classes, in_h, in_w, mode=0, sigmoid=3) -> pred [N, A, 5+nc]
+        decode_outputs, drone/models/core/utils_bbox.py:254-306 (mode 1: mmdet YOLOXHead._bbox_decode); sigmoid: bit 0
+        objectness, bit 1 classes, channels outside the mask stay raw logits (the variants of utils_bbox.py:36-253)
     glsdet::nms(pred, num_classes, box_mode, conf_thres, nms_thres, max_det) -> (dets [N,max_det,7], count [2N], status [1])
         class max + threshold + per-class NMS of non_max_suppression, utils_bbox.py:375-419
     glsdet::batched_nms(boxes, scores, idxs, iou_threshold) -> keep int64 [K]
@@ -87,7 +88,7 @@ def register():
     lib_def.define("conv_bn_act(Tensor x, Tensor w, Tensor scale, Tensor bias, int cout, int R, int S, int stride, int pad, "
                    "int act, Tensor? res=None, bool out_fp32=False) -> Tensor")
     lib_def.define("nonlocal_dot(Tensor x, Tensor tpg, int ci, Tensor wout, Tensor bout) -> Tensor")
-    lib_def.define("yolox_decode(Tensor[] levels, int num_classes, int in_h, int in_w, int mode=0) -> Tensor")
+    lib_def.define("yolox_decode(Tensor[] levels, int num_classes, int in_h, int in_w, int mode=0, int sigmoid=3) -> Tensor")
     lib_def.define("nms(Tensor pred, int num_classes, int box_mode, float conf_thres, float nms_thres, int max_det) -> "
                    "(Tensor, Tensor, Tensor)")
     lib_def.define("batched_nms(Tensor boxes, Tensor scores, Tensor idxs, float iou_threshold) -> Tensor")
@@ -139,7 +140,7 @@ def register():
         return y
 
     # ------------------------------------------------------------------ yolox_decode
-    def yolox_decode(levels, num_classes, in_h, in_w, mode=0):
+    def yolox_decode(levels, num_classes, in_h, in_w, mode=0, sigmoid=3):
         lib = _lib.load()
         _need_cuda(*levels)
         if any(l.dtype != torch.float32 for l in levels):
@@ -149,11 +150,11 @@ def register():
         out = torch.empty(n, A, 5 + num_classes, dtype=torch.float32, device=levels[0].device)
         arr = (View * len(levels))(*[_nhwc_view(l, "yolox_decode.level") for l in levels])
         strides = (C.c_int32 * len(levels))(*[in_h // l.shape[1] for l in levels]) if mode == 1 else None
-        check(lib.glsdet_yolox_decode(arr, len(levels), num_classes, in_h, in_w, strides, mode, out.data_ptr(), out.numel(),
-                                      None, _stream(out)), "yolox_decode")
+        check(lib.glsdet_yolox_decode_ex(arr, len(levels), num_classes, in_h, in_w, strides, mode, sigmoid, out.data_ptr(),
+                                         out.numel(), None, _stream(out)), "yolox_decode")
         return out
 
-    def yolox_decode_meta(levels, num_classes, in_h, in_w, mode=0):
+    def yolox_decode_meta(levels, num_classes, in_h, in_w, mode=0, sigmoid=3):
         return levels[0].new_empty((levels[0].shape[0], sum(l.shape[1] * l.shape[2] for l in levels), 5 + num_classes))
 
     # ------------------------------------------------------------------ nms

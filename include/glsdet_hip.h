@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GLSDET_ABI_VERSION 14
+#define GLSDET_ABI_VERSION 15
 
 enum { GLSDET_F16 = 0, GLSDET_F32 = 1 };
 enum { GLSDET_ACT_NONE = 0, GLSDET_ACT_SILU = 1, GLSDET_ACT_RELU = 2, GLSDET_ACT_LRELU = 3,
@@ -290,11 +290,23 @@ int glsdet_scale_by_map(const glsdet_view* x, const glsdet_view* map, const glsd
  * mode 1: sigmoid(obj,cls); x1,y1,x2,y2 in input pixels, s_l = strides[l]; if scale_factors
  *         (device fp32 [n][4], may be NULL) is given the box is divided by it per image
  *         (mmdet `rescale=True`, yolox_head.py:283-285).
+ * glsdet_yolox_decode_ex (ABI 15): the same with a choice of the score channels that go through the sigmoid --
+ *   sigmoid_mask bit 0 = objectness (channel 4), bit 1 = the classes (channels 5 .. 5+nc); a channel outside the mask
+ *   is copied through as the raw fp32 logit, bit for bit; 3 = glsdet_yolox_decode; outside 0..3: GLSDET_E_ARG.  The
+ *   box arithmetic does not depend on the mask.  The decode variants of drone/models/core/utils_bbox.py:36-253 that
+ *   the harness picks by `decode_mode` (drone/yolo.py:75-82):
+ *     decode_outputs_cls_sigmoid     mode 0, mask 2        decode_outputs_no_sigmoid   mode 0, mask 1
+ *     decode_outputs_no_sigmoid_all  mode 0, mask 0        decode_outputs_xyxy         mode 1, mask 0, strides = NULL,
+ *                                                                                      scale_factors = NULL
  */
 int glsdet_yolox_decode(const glsdet_view* levels, int32_t n_levels, int32_t num_classes,
                         int32_t in_h, int32_t in_w, const int32_t* strides /*host, may be NULL*/,
                         int32_t mode, float* out, int64_t out_elems,
                         const float* scale_factors, void* stream);
+int glsdet_yolox_decode_ex(const glsdet_view* levels, int32_t n_levels, int32_t num_classes,
+                           int32_t in_h, int32_t in_w, const int32_t* strides /*host, may be NULL*/,
+                           int32_t mode, int32_t sigmoid_mask, float* out, int64_t out_elems,
+                           const float* scale_factors, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * class-max + score threshold + batched (per-class) NMS
