@@ -383,29 +383,32 @@ struct GeoMap16Holder { static constexpr GeoMap16<TH, TW, PW, NL> map{}; };
 // optional residual.  A thread's chunks are 256 / OCPR pixels apart -- one or two tile rows -- so its addresses advance
 // by a constant: the 64-bit offsets are built once and stepped with one add per chunk (the per-chunk multiplies were
 // ~10 vector instructions each in kernels that PMC shows issue bound), and the loop is fully unrolled.
-// sum and sum of squares of one stored 16-byte chunk
-__device__ __forceinline__ void gn_chunk_sums(u32x4 v, f16*, float& s1, float& s2) {
+// sum and sum of squares of one stored 16-byte chunk, in fp64 from the first add on: the partials are documented as the
+// fp64 sums of the stored values (fp32 running sums rounded after a few dozen terms; tests/test_conv_exact.py holds the
+// partials to the exact sums)
+__device__ __forceinline__ void gn_chunk_sums(u32x4 v, f16*, double& s1, double& s2) {
   const f16x8 h = __builtin_bit_cast(f16x8, v);
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    const float f = (float)h[e];
+    const double f = (double)(float)h[e];
     s1 += f;
     s2 += f * f;
   }
 }
-__device__ __forceinline__ void gn_chunk_sums(u32x4 v, float*, float& s1, float& s2) {
+__device__ __forceinline__ void gn_chunk_sums(u32x4 v, float*, double& s1, double& s2) {
   const f32x4 h = __builtin_bit_cast(f32x4, v);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    s1 += h[e];
-    s2 += h[e] * h[e];
+    const double f = (double)h[e];
+    s1 += f;
+    s2 += f * f;
   }
 }
 // GroupNorm partials of a tile (GN instantiations only): every thread owns ONE channel chunk (cq = tid % OCPR) of several
 // pixels.  The lanes of a wave that hold chunks of the same group are folded by xor shuffles (fixed order, no LDS, no
 // barrier) and one lane per (wave, group) writes the fp64 partial: four slices per tile, one per wave.
 template <typename TO, int CO_T>
-__device__ __forceinline__ void gn_tile_partials(const ConvArgs& a, int img, int ty0, int tx0, int co0, int tid, float s1, float s2) {
+__device__ __forceinline__ void gn_tile_partials(const ConvArgs& a, int img, int ty0, int tx0, int co0, int tid, double s1, double s2) {
   constexpr int VO = 16 / (int)sizeof(TO), OCPR = CO_T / VO;
   const int cpv = a.gn_cpg / VO;                  // chunks per group: 1 (f16, 8 channels per group), 2, 4, ...
   for (int m = 1; m < cpv; m <<= 1) {
@@ -422,8 +425,8 @@ __device__ __forceinline__ void gn_tile_partials(const ConvArgs& a, int img, int
     const int tiles_x = (a.Wo + 15) / 16, tiles = tiles_x * ((a.Ho + 7) / 8);
     const int tile = (ty0 >> 3) * tiles_x + (tx0 >> 4);
     double* o = a.gn_part + ((((long)img * tiles + tile) * 4 + wave) * a.gn_groups + (co0 + lane * VO) / a.gn_cpg) * 2;
-    o[0] = (double)s1;
-    o[1] = (double)s2;
+    o[0] = s1;
+    o[1] = s2;
   }
 }
 
@@ -435,7 +438,7 @@ __device__ __forceinline__ void halo_store_tile(const unsigned char* stile, cons
   constexpr int VO = 16 / (int)sizeof(TO);
   constexpr int OCPR = CO_T / VO;                 // chunks per pixel
   constexpr int PXS = 256 / OCPR;                 // pixels between two chunks of one thread (a multiple of 16)
-  float gs1 = 0.f, gs2 = 0.f;                     // (GN) sums over this thread's stored chunks
+  double gs1 = 0., gs2 = 0.;                      // (GN) sums over this thread's stored chunks
   if (sizeof(TO) == 2 && a.res) {                 // wide staging (fp32 rows): add in fp32, round once
     constexpr int ORSW = CO_T * 4 + 16;
     for (int q = tid; q < LIVE * OCPR; q += 256) {
