@@ -105,9 +105,10 @@ __global__ __launch_bounds__(256) void upsample_add_kernel(const unsigned char* 
 
 // ---------------------------------------------------------------- GroupNorm
 // Pass 1: a workgroup owns a slice of one image's pixels; thread t always reads vector column
-// t % vcols (256 % vcols == 0), so its elements all belong to ONE group; sum and sum of
-// squares are kept in fp64 (no cancellation issue in E[x^2]-mean^2), folded per group in a
-// fixed order and written as one partial per (image, slice, group).
+// t % vcols (256 % vcols == 0), so its elements all belong to ONE group; every element is
+// widened to fp64 BEFORE it is squared and summed (an fp32 x * x carries a rounding of 2^-24 x^2
+// that E[x^2]-mean^2 amplifies by mean^2 / var: 0.5 absolute on mean 2^12, var 1), the sums are
+// folded per group in a fixed order and written as one partial per (image, slice, group).
 #define GLS_GN_SPLIT 64
 #define GLS_GN_SETS 16
 // 1..16 independent tensors of the same C / groups / image count per launch pair (the cls and reg
@@ -118,7 +119,7 @@ struct GnSet {
   long xsn, xsh, xsw, ysn, ysh, ysw;
   const float *gamma, *beta;
   double* partial;
-  float* mr;                    // [image][group] mean, rstd (gn_fold_kernel -> gn_apply_kernel)
+  double* mr;                   // [image][group] mean, rstd (gn_fold_kernel -> gn_apply_kernel)
   int H, W, nsplit, chunk, gb;
   int pstride, pre;             // partial slices per image in `partial`; pre: they were written by the producing conv
 };
@@ -144,15 +145,12 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnArgs a) {
   double sum = 0.0, sq = 0.0;
   for (int p = pbeg + r0; p < pend; p += rows) {
     const V v = *reinterpret_cast<const V*>(S.x + (b * S.xsn + (p / W) * S.xsh + (p % W) * S.xsw + cc * VN) * (long)sizeof(T));
-    float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int e = 0; e < VN; ++e) {
-      const float f = (float)v[e];
-      s1 += f;
-      s2 += f * f;
+      const double f = (double)(float)v[e];
+      sum += f;
+      sq += f * f;
     }
-    sum += (double)s1;
-    sq += (double)s2;
   }
   s_sum[threadIdx.x] = sum;
   s_sq[threadIdx.x] = sq;
@@ -198,17 +196,19 @@ __global__ __launch_bounds__(256) void gn_fold_kernel(const GnArgs a) {
     const double mean = t / cnt;
     double var = q / cnt - mean * mean;
     if (var < 0.0) var = 0.0;
-    S.mr[((long)b * groups + g) * 2] = (float)mean;
-    S.mr[((long)b * groups + g) * 2 + 1] = (float)(1.0 / sqrt(var + (double)a.eps));
+    S.mr[((long)b * groups + g) * 2] = mean;
+    S.mr[((long)b * groups + g) * 2 + 1] = 1.0 / sqrt(var + (double)a.eps);
   }
 }
 
-// Pass 3: y = act((x - mean) * rstd * gamma + beta).
+// Pass 3: y = act(x * sc + sh), sc = gamma * rstd, sh = beta - mean * sc.  sc and sh are formed in fp64 from the fp64 mean and
+// rstd and rounded to fp32 once each: where beta and mean * sc cancel, an fp32 mean, rstd or gamma * rstd leaves an error of
+// 2^-24 |mean * sc| in sh, many ulps of a small sh (and of a small result).
 template <typename T>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const GnArgs a) {
   typedef typename V16<T>::type V;
   constexpr int VN = V16<T>::N;
-  __shared__ float s_mean[256], s_rstd[256];
+  __shared__ double s_mean[256], s_rstd[256];
   const GnSet& S = a.s[blockIdx.z];
   if ((int)blockIdx.x >= S.gb) return;
   const int b = blockIdx.y;
@@ -225,9 +225,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GnArgs a) {
   float sc[VN], sh[VN];
 #pragma unroll
   for (int e = 0; e < VN; ++e) {
-    const float ga = S.gamma[cc * VN + e] * s_rstd[g];
-    sc[e] = ga;
-    sh[e] = S.beta[cc * VN + e] - s_mean[g] * ga;
+    const double ga = (double)S.gamma[cc * VN + e] * s_rstd[g];
+    sc[e] = (float)ga;
+    sh[e] = (float)((double)S.beta[cc * VN + e] - s_mean[g] * ga);
   }
   for (int p = blockIdx.x * rows + r0; p < N; p += S.gb * rows) {
     const long ox = (b * S.xsn + (p / W) * S.xsh + (p % W) * S.xsw + cc * VN) * (long)sizeof(T);
@@ -409,7 +409,7 @@ static int groupnorm_sets(const glsdet_view* x, const glsdet_view* y, int32_t n_
   OpRecord op;
   op.kind = 7;
   op.flops = op.bytes = 0;
-  const long per_set = (long)nimg * GLS_GN_SPLIT * groups * 2 + (long)nimg * groups * 2;      // doubles (the tail holds mean, rstd as floats)
+  const long per_set = (long)nimg * GLS_GN_SPLIT * groups * 2 + (long)nimg * groups * 2;      // doubles (the tail holds mean, rstd)
   for (int q = 0; q < n_sets; ++q) {
     int rc;
     if ((rc = check_view(x[q], "groupnorm.x"))) return rc;
@@ -424,7 +424,7 @@ static int groupnorm_sets(const glsdet_view* x, const glsdet_view* y, int32_t n_
     S.ysn = y[q].sn; S.ysh = y[q].sh; S.ysw = y[q].sw;
     S.gamma = gamma[q]; S.beta = beta[q];
     S.partial = (double*)stats + q * per_set;
-    S.mr = (float*)((double*)stats + q * per_set + (long)nimg * GLS_GN_SPLIT * groups * 2);
+    S.mr = (double*)stats + q * per_set + (long)nimg * GLS_GN_SPLIT * groups * 2;
     S.H = x[q].h; S.W = x[q].w;
     S.pstride = GLS_GN_SPLIT;
     S.pre = 0;
