@@ -10,7 +10,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libglsdet_hip.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 CAPTURE_LOCK = threading.RLock()        # hipGraph captures are serialised across host threads
 
 F16, F32 = 0, 1
@@ -129,6 +129,14 @@ _SIGS = {
                                     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
                                     C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int64, C.c_void_p]),
+    "glsdet_gfl_candidates_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "glsdet_gfl_candidates": (C.c_int, [C.POINTER(View), C.POINTER(View), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "glsdet_aug_merge_workspace_bytes": (C.c_int64, [C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "glsdet_aug_merge_nms": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32,
+                                       C.c_int32, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "glsdet_pil_resize_normalize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                               C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                               C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double),
@@ -139,6 +147,12 @@ _SIGS = {
                                               C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     "glsdet_resize_normalize_pad_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                                  C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
+    "glsdet_resize_normalize_pad_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                                 C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32,
+                                                 C.c_void_p]),
+    "glsdet_resize_normalize_pad_u8_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                    C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                    C.c_int32, C.c_void_p]),
     "glsdet_ufp_merge_workspace_bytes": (C.c_int64, [C.c_int32]),
     "glsdet_ufp_backmap_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_float,
                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

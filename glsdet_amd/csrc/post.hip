@@ -2,6 +2,7 @@
 // HBM / latency bound integer-and-compare work: no MFMA; coalesced reads, LDS-staged
 // tiles for the O(n^2) passes, 64-bit wave ballots as the suppression bitmask.
 #include <stdlib.h>
+#include <algorithm>
 #include <type_traits>
 #include <string.h>
 
@@ -834,6 +835,88 @@ __global__ __launch_bounds__(256) void gfl_merge_kernel(int n_levels, int max_ca
   w2.cscore[dst] = ex.w;
 }
 
+// get_bboxes(..., rescale=False, with_nms=False): the same top-k + level concatenation as gfl_merge_kernel, written out as
+// candidate rows [n][cap][8] = x1,y1,x2,y2,score,label,0,0 (two float4 per row, one thread per row) with their count.
+__global__ __launch_bounds__(256) void gfl_export_kernel(int n_levels, int max_cand1, int nms_pre, NmsWs w1,
+                                                         float4* __restrict__ cand, int cap, int* __restrict__ cand_count) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  int total = 0;
+  for (int t = 0; t < n_levels; ++t) total += min(min(w1.cnt[b * n_levels + t], max_cand1), nms_pre);
+  total = min(total, cap);
+  if (i == 0) cand_count[b] = total;
+  if (i >= total) return;
+  int start = 0, l = 0;
+  for (l = 0; l < n_levels; ++l) {
+    const int take = min(min(w1.cnt[b * n_levels + l], max_cand1), nms_pre);
+    if (i < start + take) break;
+    start += take;
+  }
+  const long src = (long)(b * n_levels + l) * max_cand1 + (i - start);
+  const float4 ex = w1.sext[src];
+  float4* d = cand + ((long)b * cap + i) * 2;
+  d[0] = w1.sbox[src];
+  d[1] = make_float4(ex.w, ex.z, 0.f, 0.f);
+}
+
+// ---------------------------------------------------------------------------- test-time augmentation
+// dense_test_mixins.py:179-206 merge_aug_bboxes + core/bbox/transforms.py:22-72 bbox_flip / bbox_mapping_back: every
+// augmentation's candidate rows are mirrored back inside ITS img_shape, divided by ITS scale factor (one fp32 operation
+// each, a true division) and concatenated in augmentation order; canchor = the concatenation index, so the NMS kernels
+// break score ties in favour of the earlier augmentation.  One thread per merged row; the K list offsets are a K-term
+// prefix sum every thread does itself.  The K (pointer, count, capacity) triples ride in the kernel arguments.
+#define GLS_MAX_AUGS 12
+struct AugArgs {
+  const float4* cand[GLS_MAX_AUGS];
+  const int* cnt[GLS_MAX_AUGS];
+  int cap[GLS_MAX_AUGS];
+  int K, n;
+  const float* meta;     // [K][n][8] = img_h, img_w, sf0..sf3, flip code, 0
+};
+
+__global__ __launch_bounds__(256) void aug_mapback_kernel(const AugArgs a, int max_cand, NmsWs w) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  int start = 0;
+  for (int k = 0; k < a.K; ++k) {                       // k is wave-uniform: the argument arrays stay scalar loads
+    const int c = min(max(a.cnt[k][b], 0), a.cap[k]);
+    if (i >= start && i < start + c) {
+      const float4* row = a.cand[k] + ((long)b * a.cap[k] + (i - start)) * 2;
+      float4 bx = row[0];
+      const float4 ex = row[1];
+      const float* m = a.meta + ((long)k * a.n + b) * 8;
+      const int flip = (int)m[6];
+      if (flip & 1) {
+        const float x1 = m[1] - bx.z, x2 = m[1] - bx.x;
+        bx.x = x1; bx.z = x2;
+      }
+      if (flip & 2) {
+        const float y1 = m[0] - bx.w, y2 = m[0] - bx.y;
+        bx.y = y1; bx.w = y2;
+      }
+      bx.x /= m[2]; bx.y /= m[3]; bx.z /= m[4]; bx.w /= m[5];
+      const long dst = (long)b * max_cand + i;
+      w.cbox[dst] = bx;
+      w.cext[dst] = make_float4(ex.x, ex.x, ex.y, ex.x);
+      w.canchor[dst] = i;
+      w.cscore[dst] = ex.x;
+    }
+    start += c;
+  }
+  if (i == 0) w.cnt[b] = start;                         // <= the sum of the capacities = max_cand
+}
+
+// `rescale=False` (dense_test_mixins.py:108-110): the kept boxes go back to augmentation 0's input scale
+__global__ __launch_bounds__(256) void aug_scale_kernel(float* __restrict__ dets, const int* __restrict__ count, int max_det,
+                                                        const float* __restrict__ out_scale) {
+  const int b = blockIdx.y;
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= min(count[b], max_det)) return;
+  float* d = dets + ((long)b * max_det + r) * 7;
+  const float* sf = out_scale + 4 * b;
+  d[0] *= sf[0]; d[1] *= sf[1]; d[2] *= sf[2]; d[3] *= sf[3];
+}
+
 // ---------------------------------------------------------------------------- UFP back-mapping
 // ufp/ufpmp_det_eval.py:282-296: a fine detection whose box lies in a chip's mosaic rectangle
 // (intersection over the smaller area > iof_thr) is mapped back through the chip's magnification
@@ -1005,6 +1088,32 @@ extern "C" int glsdet_nms(const float* pred, int32_t n, int32_t A, int32_t num_c
   return submit(std::move(op), stream);
 }
 
+// the level views of glsdet_gfl_detect / glsdet_gfl_candidates -> kernel arguments (who = the entry point, for the messages)
+static int gfl_fill_args(const glsdet_view* cls, const glsdet_view* reg, int n_levels, const int32_t* strides, int num_classes,
+                         int reg_max, int in_h, int in_w, const float* img_hw, float score_thr, const char* who,
+                         const char* cls_name, const char* reg_name, GflArgs& a, int& maxhw) {
+  a = {};
+  maxhw = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    int rc;
+    if ((rc = check_view(cls[l], cls_name, false))) return rc;
+    if ((rc = check_view(reg[l], reg_name, false))) return rc;
+    if (cls[l].dtype != GLSDET_F32 || reg[l].dtype != GLSDET_F32) GLS_FAIL(GLSDET_E_ARG, "%s: levels must be fp32", who);
+    if (cls[l].c < num_classes || reg[l].c < 4 * (reg_max + 1) || cls[l].n != cls[0].n || reg[l].n != cls[0].n ||
+        reg[l].h != cls[l].h || reg[l].w != cls[l].w || strides[l] < 1)
+      GLS_FAIL(GLSDET_E_ARG, "%s: level %d extent mismatch", who, l);
+    a.cls[l] = (const float*)cls[l].base; a.reg[l] = (const float*)reg[l].base;
+    a.csn[l] = cls[l].sn; a.csh[l] = cls[l].sh; a.csw[l] = cls[l].sw;
+    a.rsn[l] = reg[l].sn; a.rsh[l] = reg[l].sh; a.rsw[l] = reg[l].sw;
+    a.H[l] = cls[l].h; a.W[l] = cls[l].w;
+    a.stride[l] = (float)strides[l];
+    if (cls[l].h * cls[l].w > maxhw) maxhw = cls[l].h * cls[l].w;
+  }
+  a.n_levels = n_levels; a.nc = num_classes; a.reg_max = reg_max; a.n = cls[0].n;
+  a.in_h = (float)in_h; a.in_w = (float)in_w; a.thr = score_thr; a.img_hw = img_hw;
+  return 0;
+}
+
 extern "C" int64_t glsdet_gfl_workspace_bytes(int32_t n, int32_t n_levels, int32_t max_cand, int32_t nms_pre) {
   if (n < 1 || n_levels < 1 || n_levels > GLS_MAX_LEVELS || max_cand < 1 || nms_pre < 1) return 0;
   return nms_layout(n * n_levels, max_cand, nullptr, nullptr, false) + 256 +
@@ -1024,26 +1133,12 @@ extern "C" int glsdet_gfl_detect(const glsdet_view* cls, const glsdet_view* reg,
   if (max_cand > GLS_NMS_MAXW * 64 || max_cand2 > GLS_NMS_MAXW * 64)
     GLS_FAIL(GLSDET_E_ARG, "gfl_detect: max_cand / n_levels*nms_pre above %d", GLS_NMS_MAXW * 64);
   if ((uintptr_t)wsp & 255) GLS_FAIL(GLSDET_E_ALIGN, "gfl_detect: workspace must be 256-byte aligned");
-  GflArgs a = {};
-  int maxhw = 0;
-  for (int l = 0; l < n_levels; ++l) {
-    int rc;
-    if ((rc = check_view(cls[l], "gfl_detect.cls", false))) return rc;
-    if ((rc = check_view(reg[l], "gfl_detect.reg", false))) return rc;
-    if (cls[l].dtype != GLSDET_F32 || reg[l].dtype != GLSDET_F32) GLS_FAIL(GLSDET_E_ARG, "gfl_detect: levels must be fp32");
-    if (cls[l].c < num_classes || reg[l].c < 4 * (reg_max + 1) || cls[l].n != cls[0].n || reg[l].n != cls[0].n ||
-        reg[l].h != cls[l].h || reg[l].w != cls[l].w || strides[l] < 1)
-      GLS_FAIL(GLSDET_E_ARG, "gfl_detect: level %d extent mismatch", l);
-    a.cls[l] = (const float*)cls[l].base; a.reg[l] = (const float*)reg[l].base;
-    a.csn[l] = cls[l].sn; a.csh[l] = cls[l].sh; a.csw[l] = cls[l].sw;
-    a.rsn[l] = reg[l].sn; a.rsh[l] = reg[l].sh; a.rsw[l] = reg[l].sw;
-    a.H[l] = cls[l].h; a.W[l] = cls[l].w;
-    a.stride[l] = (float)strides[l];
-    if (cls[l].h * cls[l].w > maxhw) maxhw = cls[l].h * cls[l].w;
-  }
-  const int n = cls[0].n;
-  a.n_levels = n_levels; a.nc = num_classes; a.reg_max = reg_max; a.n = n;
-  a.in_h = (float)in_h; a.in_w = (float)in_w; a.thr = score_thr; a.img_hw = img_hw;
+  GflArgs a;
+  int maxhw, rc;
+  if ((rc = gfl_fill_args(cls, reg, n_levels, strides, num_classes, reg_max, in_h, in_w, img_hw, score_thr, "gfl_detect",
+                          "gfl_detect.cls", "gfl_detect.reg", a, maxhw)))
+    return rc;
+  const int n = a.n;
   NmsWs w1, w2;
   const long need1 = nms_layout(n * n_levels, max_cand, &w1, (char*)wsp, false);
   const long off2 = align_up(need1, 256);
@@ -1066,6 +1161,116 @@ extern "C" int glsdet_gfl_detect(const glsdet_view* cls, const glsdet_view* reg,
     hipLaunchKernelGGL(nms_rank_kernel, dim3((max_cand2 + 63) / 64, n), dim3(256), 0, st, max_cand2, w2);
     hipLaunchKernelGGL(nms_mask_kernel, dim3(2048, n), dim3(64), 0, st, max_cand2, nw2, iou_thr, w2);
     hipLaunchKernelGGL(nms_scan_kernel, dim3(n), dim3(1024), 0, st, max_cand2, nw2, max_det, w2, dets, count);
+    GLS_HIP(hipGetLastError());
+    return 0;
+  };
+  return submit(std::move(op), stream);
+}
+
+extern "C" int64_t glsdet_gfl_candidates_workspace_bytes(int32_t n, int32_t n_levels, int32_t max_cand) {
+  if (n < 1 || n_levels < 1 || n_levels > GLS_MAX_LEVELS || max_cand < 1) return 0;
+  return nms_layout(n * n_levels, max_cand, nullptr, nullptr, false);
+}
+
+extern "C" int glsdet_gfl_candidates(const glsdet_view* cls, const glsdet_view* reg, int32_t n_levels,
+                                     const int32_t* strides, int32_t num_classes, int32_t reg_max, int32_t in_h,
+                                     int32_t in_w, const float* img_hw, float score_thr, int32_t nms_pre,
+                                     int32_t max_cand, float* cand, int32_t cap, int32_t* cand_count, int32_t* status,
+                                     void* wsp, int64_t ws_bytes, void* stream) {
+  if (!cls || !reg || !strides || !cand || !cand_count || !status || !wsp)
+    GLS_FAIL(GLSDET_E_ARG, "gfl_candidates: null argument");
+  if (n_levels < 1 || n_levels > GLS_MAX_LEVELS || num_classes < 1 || reg_max < 1 || reg_max > 63 || nms_pre < 1 ||
+      max_cand < 1)
+    GLS_FAIL(GLSDET_E_ARG, "gfl_candidates: bad sizes");
+  if (max_cand > GLS_NMS_MAXW * 64) GLS_FAIL(GLSDET_E_ARG, "gfl_candidates: max_cand above %d", GLS_NMS_MAXW * 64);
+  if (((uintptr_t)wsp & 255) || ((uintptr_t)cand & 15))
+    GLS_FAIL(GLSDET_E_ALIGN, "gfl_candidates: workspace must be 256-byte and cand 16-byte aligned");
+  GflArgs a;
+  int maxhw, rc;
+  if ((rc = gfl_fill_args(cls, reg, n_levels, strides, num_classes, reg_max, in_h, in_w, img_hw, score_thr,
+                          "gfl_candidates", "gfl_candidates.cls", "gfl_candidates.reg", a, maxhw)))
+    return rc;
+  const int n = a.n;
+  long need_cap = 0;
+  for (int l = 0; l < n_levels; ++l) need_cap += std::min((long)nms_pre, (long)a.H[l] * a.W[l] * num_classes);
+  if (cap < need_cap)
+    GLS_FAIL(GLSDET_E_CAPACITY, "gfl_candidates: cap %d < sum over levels of min(nms_pre, H*W*nc) = %ld", cap, need_cap);
+  NmsWs w1;
+  const long need = nms_layout(n * n_levels, max_cand, &w1, (char*)wsp, false);
+  if (ws_bytes < need) GLS_FAIL(GLSDET_E_CAPACITY, "gfl_candidates: workspace %ld < %ld bytes", (long)ws_bytes, need);
+  double bytes = 0;
+  for (int l = 0; l < n_levels; ++l) bytes += (double)n * a.H[l] * a.W[l] * (num_classes + 4.0 * (reg_max + 1)) * 4.0;
+  OpRecord op;
+  op.kind = 6;
+  op.flops = 0;
+  op.bytes = bytes;
+  op.name = "gfl_candidates(filter+topk+export)";
+  op.launch = [=](hipStream_t st) -> int {
+    hipLaunchKernelGGL(reset_counters_kernel, dim3(1), dim3(256), 0, st, w1.cnt, n * n_levels, status);
+    hipLaunchKernelGGL(gfl_filter_kernel, dim3((maxhw + 255) / 256, n, n_levels), dim3(256), 0, st, a, max_cand, w1, status);
+    hipLaunchKernelGGL(nms_rank_kernel, dim3((max_cand + 63) / 64, n * n_levels), dim3(256), 0, st, max_cand, w1);
+    hipLaunchKernelGGL(gfl_export_kernel, dim3((cap + 255) / 256, n), dim3(256), 0, st, n_levels, max_cand, nms_pre, w1,
+                       (float4*)cand, cap, cand_count);
+    GLS_HIP(hipGetLastError());
+    return 0;
+  };
+  return submit(std::move(op), stream);
+}
+
+static long aug_total_cap(const int32_t* caps, int K) {
+  long t = 0;
+  for (int k = 0; k < K; ++k) t += caps[k] > 0 ? caps[k] : 0;
+  return t;
+}
+
+extern "C" int64_t glsdet_aug_merge_workspace_bytes(int32_t n, const int32_t* caps, int32_t n_augs) {
+  if (n < 1 || !caps || n_augs < 1 || n_augs > GLS_MAX_AUGS) return 0;
+  const long total = aug_total_cap(caps, n_augs);
+  if (total < 1 || total > GLS_NMS_MAXW * 64) return 0;
+  return nms_layout(n, (int)total, nullptr, nullptr, true);
+}
+
+extern "C" int glsdet_aug_merge_nms(const float* const* cands, const int32_t* const* cand_counts, const int32_t* caps,
+                                    int32_t n_augs, int32_t n, const float* aug_meta, float iou_thr, int32_t max_det,
+                                    const float* out_scale, float* dets, int32_t* count, int32_t* status, void* wsp,
+                                    int64_t ws_bytes, void* stream) {
+  if (!cands || !cand_counts || !caps || !aug_meta || !dets || !count || !status || !wsp)
+    GLS_FAIL(GLSDET_E_ARG, "aug_merge_nms: null argument");
+  if (n_augs < 1 || n_augs > GLS_MAX_AUGS)
+    GLS_FAIL(GLSDET_E_ARG, "aug_merge_nms: %d augmentations, need 1 .. GLSDET_MAX_AUGS = %d", n_augs, GLS_MAX_AUGS);
+  if (n < 1 || max_det < 1) GLS_FAIL(GLSDET_E_ARG, "aug_merge_nms: bad sizes");
+  AugArgs a = {};
+  for (int k = 0; k < n_augs; ++k) {
+    if (!cands[k] || !cand_counts[k] || caps[k] < 1) GLS_FAIL(GLSDET_E_ARG, "aug_merge_nms: augmentation %d: null list or cap < 1", k);
+    if ((uintptr_t)cands[k] & 15) GLS_FAIL(GLSDET_E_ALIGN, "aug_merge_nms: augmentation %d: candidate rows must be 16-byte aligned", k);
+    a.cand[k] = (const float4*)cands[k];
+    a.cnt[k] = cand_counts[k];
+    a.cap[k] = caps[k];
+  }
+  const long total = aug_total_cap(caps, n_augs);
+  if (total > GLS_NMS_MAXW * 64)
+    GLS_FAIL(GLSDET_E_ARG, "aug_merge_nms: the candidate capacities sum to %ld, above the NMS limit of %d; lower nms_pre", total,
+             GLS_NMS_MAXW * 64);
+  if ((uintptr_t)wsp & 255) GLS_FAIL(GLSDET_E_ALIGN, "aug_merge_nms: workspace must be 256-byte aligned");
+  a.K = n_augs; a.n = n; a.meta = aug_meta;
+  const int max_cand = (int)total;
+  NmsWs w;
+  const long need = nms_layout(n, max_cand, &w, (char*)wsp, true);
+  if (ws_bytes < need) GLS_FAIL(GLSDET_E_CAPACITY, "aug_merge_nms: workspace %ld < %ld bytes", (long)ws_bytes, need);
+  const int nw = (max_cand + 63) / 64;
+  OpRecord op;
+  op.kind = 6;
+  op.flops = 0;
+  op.bytes = (double)n * max_cand * 64.0;
+  op.name = "aug_merge_nms(map back+concat+nms)";
+  op.launch = [=](hipStream_t st) -> int {
+    hipLaunchKernelGGL(reset_counters_kernel, dim3(1), dim3(256), 0, st, w.cnt, 2 * n, status);
+    hipLaunchKernelGGL(aug_mapback_kernel, dim3((max_cand + 255) / 256, n), dim3(256), 0, st, a, max_cand, w);
+    hipLaunchKernelGGL(nms_rank_kernel, dim3((max_cand + 63) / 64, n), dim3(256), 0, st, max_cand, w);
+    hipLaunchKernelGGL(nms_mask_kernel, dim3(2048, n), dim3(64), 0, st, max_cand, nw, iou_thr, w);
+    hipLaunchKernelGGL(nms_scan_kernel, dim3(n), dim3(1024), 0, st, max_cand, nw, max_det, w, dets, count);
+    if (out_scale)
+      hipLaunchKernelGGL(aug_scale_kernel, dim3((max_det + 255) / 256, n), dim3(256), 0, st, dets, count, max_det, out_scale);
     GLS_HIP(hipGetLastError());
     return 0;
   };

@@ -76,16 +76,19 @@ struct NormArgs3 {
   double mean[3], stdinv[3];
 };
 __global__ __launch_bounds__(256) void resize_norm_pad_kernel(const float* __restrict__ src, int h, int w, int nh, int nw,
-                                                              float* __restrict__ dst, int ph, int pw, const NormArgs3 na) {
+                                                              float* __restrict__ dst, int ph, int pw, const NormArgs3 na,
+                                                              int flip) {
   const long total = (long)ph * pw;
   for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     const int x = (int)(p % pw), y = (int)(p / pw);
     float v[3] = {0.f, 0.f, 0.f};
     if (x < nw && y < nh) {
+      // mmcv.imflip of the resized picture (bit 0 horizontal, bit 1 vertical): this pixel is the unflipped one at (ys, xs)
+      const int xs = (flip & 1) ? nw - 1 - x : x, ys = (flip & 2) ? nh - 1 - y : y;
       int x0, x1, y0, y1;
       float fx, fy;
-      lin_tap_f(x, nw, w, x0, x1, fx);
-      lin_tap_f(y, nh, h, y0, y1, fy);
+      lin_tap_f(xs, nw, w, x0, x1, fx);
+      lin_tap_f(ys, nh, h, y0, y1, fy);
 #pragma unroll
       for (int e = 0; e < 3; ++e) {
         const double a = (double)src[((long)y0 * w + x0) * 3 + e] * (1.0 - (double)fx) + (double)src[((long)y0 * w + x1) * 3 + e] * (double)fx;
@@ -106,23 +109,24 @@ __global__ __launch_bounds__(256) void resize_norm_pad_kernel(const float* __res
 // works in 11-bit fixed point on uint8 and rounds to uint8 before Normalize sees the pixel.
 __global__ __launch_bounds__(256) void resize_norm_pad_u8_kernel(const unsigned char* __restrict__ src, int h, int w, int nh,
                                                                  int nw, float* __restrict__ dst, int ph, int pw,
-                                                                 const NormArgs3 na) {
+                                                                 const NormArgs3 na, int flip) {
   const long total = (long)ph * pw;
   const bool same = nh == h && nw == w;                            // cv2.resize returns a copy
   for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     const int x = (int)(p % pw), y = (int)(p / pw);
     float v[3] = {0.f, 0.f, 0.f};
     if (x < nw && y < nh) {
+      const int xs = (flip & 1) ? nw - 1 - x : x, ys = (flip & 2) ? nh - 1 - y : y;     // as in resize_norm_pad_kernel
       LinTap tx, ty;
       if (!same) {
-        tx = lin_tap_u8(x, nw, w);
-        ty = lin_tap_u8(y, nh, h);
+        tx = lin_tap_u8(xs, nw, w);
+        ty = lin_tap_u8(ys, nh, h);
       }
 #pragma unroll
       for (int e = 0; e < 3; ++e) {
         int q;
         if (same) {
-          q = src[((long)y * w + x) * 3 + e];
+          q = src[((long)ys * w + xs) * 3 + e];
         } else {
           const int r0 = src[((long)ty.i0 * w + tx.i0) * 3 + e] * tx.c0 + src[((long)ty.i0 * w + tx.i1) * 3 + e] * tx.c1;
           const int r1 = src[((long)ty.i1 * w + tx.i0) * 3 + e] * tx.c0 + src[((long)ty.i1 * w + tx.i1) * 3 + e] * tx.c1;
@@ -163,11 +167,13 @@ extern "C" int glsdet_ufp_mosaic(const unsigned char* img, int32_t H, int32_t W,
   return submit(std::move(op), stream);
 }
 
-extern "C" int glsdet_resize_normalize_pad(const float* src, int32_t h, int32_t w, int32_t nh, int32_t nw, float* dst,
+extern "C" int glsdet_resize_normalize_pad_ex(const float* src, int32_t h, int32_t w, int32_t nh, int32_t nw, float* dst,
                                            int32_t ph, int32_t pw, const double* mean_rgb, const double* std_rgb,
-                                           void* stream) {
+                                           int32_t flip, void* stream) {
   if (!src || !dst || !mean_rgb || !std_rgb) GLS_FAIL(GLSDET_E_ARG, "resize_normalize_pad: null argument");
   if (h < 1 || w < 1 || nh < 1 || nw < 1 || ph < nh || pw < nw) GLS_FAIL(GLSDET_E_ARG, "resize_normalize_pad: bad sizes");
+  if (flip < 0 || flip > 3)
+    GLS_FAIL(GLSDET_E_ARG, "resize_normalize_pad: flip %d is not 0 (none), 1 (horizontal), 2 (vertical) or 3 (diagonal)", flip);
   NormArgs3 na;
   for (int c = 0; c < 3; ++c) {
     na.mean[c] = mean_rgb[c];
@@ -181,18 +187,26 @@ extern "C" int glsdet_resize_normalize_pad(const float* src, int32_t h, int32_t 
   op.launch = [=](hipStream_t st) -> int {
     long g = ((long)ph * pw + 255) / 256;
     if (g > 65535) g = 65535;
-    hipLaunchKernelGGL(resize_norm_pad_kernel, dim3((unsigned)g), dim3(256), 0, st, src, h, w, nh, nw, dst, ph, pw, na);
+    hipLaunchKernelGGL(resize_norm_pad_kernel, dim3((unsigned)g), dim3(256), 0, st, src, h, w, nh, nw, dst, ph, pw, na, flip);
     GLS_HIP(hipGetLastError());
     return 0;
   };
   return submit(std::move(op), stream);
 }
 
-extern "C" int glsdet_resize_normalize_pad_u8(const unsigned char* src, int32_t h, int32_t w, int32_t nh, int32_t nw,
+extern "C" int glsdet_resize_normalize_pad(const float* src, int32_t h, int32_t w, int32_t nh, int32_t nw, float* dst,
+                                           int32_t ph, int32_t pw, const double* mean_rgb, const double* std_rgb,
+                                           void* stream) {
+  return glsdet_resize_normalize_pad_ex(src, h, w, nh, nw, dst, ph, pw, mean_rgb, std_rgb, 0, stream);
+}
+
+extern "C" int glsdet_resize_normalize_pad_u8_ex(const unsigned char* src, int32_t h, int32_t w, int32_t nh, int32_t nw,
                                               float* dst, int32_t ph, int32_t pw, const double* mean_rgb,
-                                              const double* std_rgb, void* stream) {
+                                              const double* std_rgb, int32_t flip, void* stream) {
   if (!src || !dst || !mean_rgb || !std_rgb) GLS_FAIL(GLSDET_E_ARG, "resize_normalize_pad_u8: null argument");
   if (h < 1 || w < 1 || nh < 1 || nw < 1 || ph < nh || pw < nw) GLS_FAIL(GLSDET_E_ARG, "resize_normalize_pad_u8: bad sizes");
+  if (flip < 0 || flip > 3)
+    GLS_FAIL(GLSDET_E_ARG, "resize_normalize_pad_u8: flip %d is not 0 (none), 1 (horizontal), 2 (vertical) or 3 (diagonal)", flip);
   NormArgs3 na;
   for (int c = 0; c < 3; ++c) {
     na.mean[c] = mean_rgb[c];
@@ -206,9 +220,15 @@ extern "C" int glsdet_resize_normalize_pad_u8(const unsigned char* src, int32_t 
   op.launch = [=](hipStream_t st) -> int {
     long g = ((long)ph * pw + 255) / 256;
     if (g > 65535) g = 65535;
-    hipLaunchKernelGGL(resize_norm_pad_u8_kernel, dim3((unsigned)g), dim3(256), 0, st, src, h, w, nh, nw, dst, ph, pw, na);
+    hipLaunchKernelGGL(resize_norm_pad_u8_kernel, dim3((unsigned)g), dim3(256), 0, st, src, h, w, nh, nw, dst, ph, pw, na, flip);
     GLS_HIP(hipGetLastError());
     return 0;
   };
   return submit(std::move(op), stream);
+}
+
+extern "C" int glsdet_resize_normalize_pad_u8(const unsigned char* src, int32_t h, int32_t w, int32_t nh, int32_t nw,
+                                              float* dst, int32_t ph, int32_t pw, const double* mean_rgb,
+                                              const double* std_rgb, void* stream) {
+  return glsdet_resize_normalize_pad_u8_ex(src, h, w, nh, nw, dst, ph, pw, mean_rgb, std_rgb, 0, stream);
 }

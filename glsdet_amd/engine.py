@@ -1002,6 +1002,68 @@ class Engine:
                                          nb["ws"].data_ptr(), nb["ws"].numel(), _stream_ptr(self.stream)), "gfl_detect")
         return nb["dets"], nb["count"], nb["status"]
 
+    @staticmethod
+    def gfl_candidate_cap(level_hw: Sequence[Tuple[int, int]], num_classes: int, nms_pre: int) -> int:
+        """Rows per image of a candidate buffer: sum over the levels of min(nms_pre, H*W*nc)."""
+        return sum(min(nms_pre, h * w * num_classes) for h, w in level_hw)
+
+    def gfl_candidate_buffers(self, n: int, n_levels: int, max_cand: int, nms_pre: int, cap: int,
+                              ws: Optional[torch.Tensor] = None):
+        """Buffers of gfl_candidates.  Augmentations that share a plan share `ws` (their launches are ordered on one
+        stream) and keep private `cand` / `cand_count`."""
+        if ws is None:
+            ws = self.raw(self.lib.glsdet_gfl_candidates_workspace_bytes(n, n_levels, max_cand))
+        return {"ws": ws, "n": n, "max_cand": max_cand, "nms_pre": nms_pre, "cap": cap,
+                "cand": torch.zeros(n, cap, 8, dtype=torch.float32, device=self.device),
+                "cand_count": torch.zeros(n, dtype=torch.int32, device=self.device),
+                "status": torch.zeros(1, dtype=torch.int32, device=self.device)}
+
+    def gfl_candidates(self, cls: Sequence[TView], reg: Sequence[TView], strides: Sequence[int], num_classes: int,
+                       reg_max: int, in_h: int, in_w: int, score_thr: float, cb, img_hw: Optional[torch.Tensor] = None):
+        """glsdet_gfl_candidates: get_bboxes(..., rescale=False, with_nms=False) into cb (gfl_candidate_buffers)."""
+        L = len(cls)
+        ca = (View * L)(*[l.as_c() for l in cls])
+        ra = (View * L)(*[l.as_c() for l in reg])
+        st = (C.c_int32 * L)(*strides)
+        assert img_hw is None or (img_hw.dtype == torch.float32 and img_hw.is_contiguous() and img_hw.numel() == 2 * cb["n"])
+        check(self.lib.glsdet_gfl_candidates(ca, ra, L, st, num_classes, reg_max, in_h, in_w,
+                                             img_hw.data_ptr() if img_hw is not None else None, score_thr,
+                                             cb["nms_pre"], cb["max_cand"], cb["cand"].data_ptr(), cb["cap"],
+                                             cb["cand_count"].data_ptr(), cb["status"].data_ptr(), cb["ws"].data_ptr(),
+                                             cb["ws"].numel(), _stream_ptr(self.stream)), "gfl_candidates")
+        return cb["cand"], cb["cand_count"], cb["status"]
+
+    def aug_merge_buffers(self, n: int, caps: Sequence[int], max_det: int):
+        K = len(caps)
+        nbytes = self.lib.glsdet_aug_merge_workspace_bytes(n, (C.c_int32 * K)(*caps), K)
+        if nbytes <= 0:
+            raise _lib.GlsdetError("aug_merge_nms: %d augmentations with candidate capacities summing to %d; at most %d "
+                              "augmentations and 32768 candidates per image (lower nms_pre)" % (K, sum(caps), 12))
+        return {"ws": self.raw(nbytes), "n": n, "caps": tuple(caps), "max_det": max_det,
+                "meta": torch.zeros(K, n, 8, dtype=torch.float32, device=self.device),
+                "out_scale": torch.ones(n, 4, dtype=torch.float32, device=self.device),
+                "dets": torch.zeros(n, max_det, 7, dtype=torch.float32, device=self.device),
+                "count": torch.zeros(2 * n, dtype=torch.int32, device=self.device),
+                "status": torch.zeros(1, dtype=torch.int32, device=self.device)}
+
+    def aug_merge_nms(self, cands: Sequence[torch.Tensor], counts: Sequence[torch.Tensor], iou_thr: float, mb,
+                      use_out_scale: bool = False):
+        """glsdet_aug_merge_nms over K candidate lists ([n, cap_k, 8] fp32 + int32 [n] counts); the per-augmentation
+        meta rows and the output scale are read from mb["meta"] / mb["out_scale"] when the launch runs."""
+        K, n = len(cands), mb["n"]
+        assert K == len(counts) == len(mb["caps"])
+        for t, c, cap in zip(cands, counts, mb["caps"]):
+            assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, cap, 8)
+            assert c.dtype == torch.int32 and c.is_contiguous() and c.numel() == n
+        pa = (C.c_void_p * K)(*[t.data_ptr() for t in cands])
+        pc = (C.c_void_p * K)(*[t.data_ptr() for t in counts])
+        check(self.lib.glsdet_aug_merge_nms(pa, pc, (C.c_int32 * K)(*mb["caps"]), K, n, mb["meta"].data_ptr(), iou_thr,
+                                            mb["max_det"], mb["out_scale"].data_ptr() if use_out_scale else None,
+                                            mb["dets"].data_ptr(), mb["count"].data_ptr(), mb["status"].data_ptr(),
+                                            mb["ws"].data_ptr(), mb["ws"].numel(), _stream_ptr(self.stream)),
+              "aug_merge_nms")
+        return mb["dets"], mb["count"], mb["status"]
+
     def branch(self, b: int):
         """Ops emitted until the next branch(0) belong to independent branch b (1..8): quadrant
         convs, the l/r/t/b stitch convs, the cls/reg towers.  No-op outside plan recording."""

@@ -298,7 +298,10 @@ class YOLOX(nn.Module):
         if len(imgs) != len(img_metas):
             raise ValueError("num of augmentations ({}) != num of image meta ({})".format(len(imgs), len(img_metas)))
         if len(imgs) != 1:
-            raise NotImplementedError("test-time augmentation is outside the hot path")
+            # the reference cannot either: BBoxTestMixin.aug_test_bboxes asserts that the head's get_bboxes and
+            # _get_bboxes_single take `with_nms` (dense_heads/dense_test_mixins.py:68), and YOLOXHead's do not
+            raise NotImplementedError("YOLOXHead does not support test-time augmentation (the reference asserts so at "
+                                      "mmdet/models/dense_heads/dense_test_mixins.py:68); GFL / MPDet do")
         return self.simple_test(imgs[0], img_metas[0], **kwargs)
 
     def extract_feat(self, img):

@@ -236,23 +236,34 @@ class SingleStageDetector(nn.Module):
                 raise TypeError("{} must be a list, but got {}".format(name, type(var)))
         if len(imgs) != len(img_metas):
             raise ValueError("num of augmentations ({}) != num of image meta ({})".format(len(imgs), len(img_metas)))
-        if len(imgs) != 1:
-            raise NotImplementedError("test-time augmentation is outside the hot path")
-        return self.simple_test(imgs[0], img_metas[0], **kwargs)
+        if len(imgs) == 1:
+            return self.simple_test(imgs[0], img_metas[0], **kwargs)
+        if imgs[0].size(0) != 1:                                   # detectors/base.py:149
+            raise AssertionError("aug test does not support inference with batch size {}".format(imgs[0].size(0)))
+        return self.aug_test(imgs, img_metas, **kwargs)
 
     def simple_test(self, img, img_metas, rescale=False):
+        kw = self._test_kwargs()
+        res = self._detector().detect(img.to("cuda", torch.float32), img_shapes=[m["img_shape"] for m in img_metas],
+                                      scale_factors=[np.asarray(m["scale_factor"], np.float32).reshape(-1)[:4]
+                                                     for m in img_metas] if rescale else None, **kw)
+        return [bbox2result(d, l, self.bbox_head.num_classes) for d, l in res]
+
+    def _test_kwargs(self):
         if self.training:
             raise NotImplementedError("call .eval(): inference only")
         cfg = self.bbox_head.test_cfg or self.test_cfg
         if cfg is None:
             raise ValueError("test_cfg (score_thr, nms, nms_pre, max_per_img) is required")
-        det = self._detector()
-        res = det.detect(img.to("cuda", torch.float32), score_thr=float(cfg["score_thr"]),
-                         iou_thr=float(cfg["nms"]["iou_threshold"]), nms_pre=int(cfg.get("nms_pre", -1)) if
-                         int(cfg.get("nms_pre", -1)) > 0 else 1000, max_per_img=int(cfg.get("max_per_img", 100)),
-                         img_shapes=[m["img_shape"] for m in img_metas],
-                         scale_factors=[np.asarray(m["scale_factor"], np.float32).reshape(-1)[:4] for m in img_metas]
-                         if rescale else None)
+        nms_pre = int(cfg.get("nms_pre", -1))
+        return dict(score_thr=float(cfg["score_thr"]), iou_thr=float(cfg["nms"]["iou_threshold"]),
+                    nms_pre=nms_pre if nms_pre > 0 else 1000, max_per_img=int(cfg.get("max_per_img", 100)))
+
+    def aug_test(self, imgs, img_metas, rescale=False):
+        """single_stage.py:110-139 -> AnchorHead.aug_test -> BBoxTestMixin.aug_test_bboxes (dense_test_mixins.py:41-114):
+        per augmentation get_bboxes(rescale=False, with_nms=False), bbox_mapping_back, one batched_nms over the union."""
+        res = self._detector().detect_aug([im.to("cuda", torch.float32) for im in imgs], img_metas, rescale=rescale,
+                                          **self._test_kwargs())
         return [bbox2result(d, l, self.bbox_head.num_classes) for d, l in res]
 
 

@@ -711,6 +711,7 @@ class HipGflDetector:
         else:
             self.num_classes = len(self.cfg["proxies_list"])
         self._compiled: Dict[Tuple, _Compiled] = {}
+        self._aug: Dict[Tuple, dict] = {}         # detect_aug: private candidate buffers + merge buffers
         self._cache_lock = threading.Lock()       # plan cache: looked up / LRU-touched / evicted by several lanes' threads
 
     def _emit(self, eng: Engine, img: torch.Tensor, trace: Optional[dict] = None):
@@ -731,7 +732,8 @@ class HipGflDetector:
     def compile(self, n: int, H: int, W: int, post: Optional[dict] = None, use_graph: bool = False,
                 instance: int = 0) -> _Compiled:
         """post: None or dict(score_thr, iou_thr, nms_pre=1000, max_per_img=100, max_cand, rescale=False)
-        (the reference's test_cfg keys, base_dense_head.py:168,295-298)."""
+        (the reference's test_cfg keys, base_dense_head.py:168,295-298).  post = dict(score_thr, nms_pre, max_cand,
+        with_nms=False) records the candidate exit instead (Engine.gfl_candidates): c.nb then holds cand / cand_count."""
         key = (n, H, W, tuple(sorted(post.items())) if post else None, use_graph, instance)
         with self._cache_lock:
             if key in self._compiled:
@@ -747,7 +749,16 @@ class HipGflDetector:
         c.plan = eng.new_plan()
         with c.plan:
             c.cls, c.reg = self._emit(eng, c.img)
-            if post is not None:
+            if post is not None and not post.get("with_nms", True):
+                # get_bboxes(..., rescale=False, with_nms=False): the candidate rows of one augmentation (detect_aug)
+                L = len(c.cls)
+                biggest = max(l.h * l.w for l in c.cls) * self.num_classes
+                nms_pre = post.get("nms_pre", 1000)
+                cap = eng.gfl_candidate_cap([(l.h, l.w) for l in c.cls], self.num_classes, nms_pre)
+                c.nb = eng.gfl_candidate_buffers(n, L, min(post.get("max_cand", 8192), biggest), nms_pre, cap)
+                eng.gfl_candidates(c.cls, c.reg, self.cfg["strides"][:L], self.num_classes, self.cfg["reg_max"], H, W,
+                                   post["score_thr"], c.nb, img_hw=c.img_hw)
+            elif post is not None:
                 L = len(c.cls)
                 biggest = max(l.h * l.w for l in c.cls) * self.num_classes
                 c.nb = eng.gfl_buffers(n, L, min(post.get("max_cand", 8192), biggest), post.get("nms_pre", 1000),
@@ -853,4 +864,61 @@ class HipGflDetector:
         for i in range(n):
             d = dets[i, : count[i]]
             out.append((d[:, :5].copy(), d[:, 6].astype(np.int64)))
+        return out
+
+    # ------------------------------------------------------------------ test-time augmentation
+    FLIP_CODES = {None: 0, "horizontal": 1, "vertical": 2, "diagonal": 3}
+
+    def _aug_state(self, n: int, caps: Tuple[int, ...], max_per_img: int):
+        """Private candidate buffers of the K augmentations and the merge buffers, one set per (n, capacities, max_det)."""
+        key = (n, caps, max_per_img)
+        with self._cache_lock:
+            st = self._aug.get(key)
+        if st is None:
+            eng = Engine(self.dtype, self.device)
+            st = dict(eng=eng, mb=eng.aug_merge_buffers(n, caps, max_per_img),
+                      cand=[torch.zeros(n, cap, 8, dtype=torch.float32, device=eng.device) for cap in caps],
+                      count=[torch.zeros(n, dtype=torch.int32, device=eng.device) for _ in caps],
+                      status=torch.zeros(len(caps), dtype=torch.int32, device=eng.device))
+            with self._cache_lock:
+                self._aug[key] = st
+        return st
+
+    def detect_aug(self, imgs: Sequence[torch.Tensor], metas: Sequence[Sequence[dict]], score_thr: float = 0.05,
+                   iou_thr: float = 0.6, nms_pre: int = 1000, max_per_img: int = 100, rescale: bool = False,
+                   use_graph: bool = False):
+        """BBoxTestMixin.aug_test_bboxes (dense_test_mixins.py:41-114): imgs[k] is augmentation k of the batch
+        ([n,3,H_k,W_k]), metas[k][i] its meta for image i (img_shape, scale_factor, flip, flip_direction).  Every
+        augmentation runs the plan of its (n, H, W) up to the candidate exit -- a flip pair shares the plan -- and
+        keeps its rows in a private buffer; one aug_merge_nms maps them back, merges and suppresses.  rescale=False
+        returns the boxes at augmentation 0's input scale, like the reference.  -> as detect()."""
+        K, n = len(imgs), imgs[0].shape[0]
+        assert K == len(metas) and K >= 1 and all(len(m) == n and im.shape[0] == n for m, im in zip(metas, imgs))
+        post = dict(score_thr=score_thr, nms_pre=nms_pre, with_nms=False)
+        plans = [self.compile(n, im.shape[2], im.shape[3], post, use_graph=use_graph) for im in imgs]
+        st = self._aug_state(n, tuple(c.nb["cap"] for c in plans), max_per_img)
+        meta = np.zeros((K, n, 8), np.float32)
+        for k in range(K):
+            for i, m in enumerate(metas[k]):
+                direction = m.get("flip_direction") if m.get("flip") else None
+                if direction not in self.FLIP_CODES:
+                    raise ValueError("flip_direction %r is not horizontal / vertical / diagonal" % (direction,))
+                meta[k, i, 0:2] = m["img_shape"][:2]
+                meta[k, i, 2:6] = np.asarray(m["scale_factor"], np.float32).reshape(4)
+                meta[k, i, 6] = self.FLIP_CODES[direction]
+        mb, dev = st["mb"], st["eng"].device
+        mb["meta"].copy_(torch.from_numpy(meta), non_blocking=True)
+        if not rescale:
+            mb["out_scale"].copy_(torch.from_numpy(meta[0, :, 2:6].copy()), non_blocking=True)
+        for k, (c, im) in enumerate(zip(plans, imgs)):
+            self.run(c, im.to(dev, torch.float32), torch.from_numpy(meta[k, :, 0:2].copy()).to(dev))
+            st["cand"][k].copy_(c.nb["cand"], non_blocking=True)
+            st["count"][k].copy_(c.nb["cand_count"], non_blocking=True)
+            st["status"][k:k + 1].copy_(c.nb["status"], non_blocking=True)
+        st["eng"].aug_merge_nms(st["cand"], st["count"], iou_thr, mb, use_out_scale=not rescale)
+        m = _Compiled()
+        m.nb = mb
+        out = self.collect(m)
+        if int(st["status"].cpu().numpy().max()) & 1:
+            raise RuntimeError("GFL candidate capacity exceeded on a level (raise max_cand)")
         return out

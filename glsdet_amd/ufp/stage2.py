@@ -60,21 +60,30 @@ class UfpSecondStage:
         return canvas
 
     # ---- Resize(keep_ratio) -> Normalize(to_rgb) -> Pad -> ImageToTensor
-    def pipeline_input(self, img_bgr: torch.Tensor):
+    FLIP_CODES = {None: 0, "horizontal": 1, "vertical": 2, "diagonal": 3}      # mmcv.imflip's directions
+
+    def pipeline_input(self, img_bgr: torch.Tensor, img_scale=None, flip=None):
         """HWC BGR image on the device -> (fp32 [1,3,ph,pw], meta dict as mmdet's img_metas).
         uint8 (a decoded frame, the first stage): cv2's uint8 fixed-point resize, rounded to uint8 before
-        Normalize; float32 (the mosaic, a float array in the reference): float bilinear."""
+        Normalize; float32 (the mosaic, a float array in the reference): float bilinear.
+        img_scale: another (long edge, short edge) than the stage's; flip: None / False, or 'horizontal' / 'vertical' /
+        'diagonal' -- RandomFlip mirrors the resized picture before Normalize and Pad (transforms.py:457-461), so the
+        padding stays at the right and the bottom and scale_factor / img_shape are those of the unflipped call."""
         assert img_bgr.dtype in (torch.float32, torch.uint8) and img_bgr.is_contiguous() and img_bgr.dim() == 3
+        flip = flip or None
+        if flip not in self.FLIP_CODES:
+            raise ValueError("flip must be None, 'horizontal', 'vertical' or 'diagonal', not %r" % (flip,))
         h, w = int(img_bgr.shape[0]), int(img_bgr.shape[1])
-        nw, nh = rescale_size((w, h), self.img_scale)
+        nw, nh = rescale_size((w, h), self.img_scale if img_scale is None else tuple(img_scale))
         ph, pw = int(math.ceil(nh / self.div)) * self.div, int(math.ceil(nw / self.div)) * self.div
         out = torch.empty(1, 3, ph, pw, dtype=torch.float32, device=self.device)
-        fn = self.lib.glsdet_resize_normalize_pad if img_bgr.dtype == torch.float32 else self.lib.glsdet_resize_normalize_pad_u8
-        _lib.check(fn(img_bgr.data_ptr(), h, w, nh, nw, out.data_ptr(), ph, pw, self._mean, self._std, self._stream()),
-                   "resize_normalize_pad")
+        fn = self.lib.glsdet_resize_normalize_pad_ex if img_bgr.dtype == torch.float32 else self.lib.glsdet_resize_normalize_pad_u8_ex
+        _lib.check(fn(img_bgr.data_ptr(), h, w, nh, nw, out.data_ptr(), ph, pw, self._mean, self._std, self.FLIP_CODES[flip],
+                      self._stream()), "resize_normalize_pad")
         torch.cuda.current_stream().synchronize()
         sf = np.array([nw / w, nh / h, nw / w, nh / h], dtype=np.float32)
-        return out, dict(img_shape=(nh, nw, 3), pad_shape=(ph, pw, 3), ori_shape=(h, w, 3), scale_factor=sf, flip=False)
+        return out, dict(img_shape=(nh, nw, 3), pad_shape=(ph, pw, 3), ori_shape=(h, w, 3), scale_factor=sf,
+                         flip=flip is not None, flip_direction=flip)
 
     # ---- back-mapping + merge NMS, ufpmp_det_eval.py:282-300
     def merge(self, dets: torch.Tensor, count: torch.Tensor, chips: Sequence[Sequence[float]], num_classes: int,

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GLSDET_ABI_VERSION 15
+#define GLSDET_ABI_VERSION 16
 
 enum { GLSDET_F16 = 0, GLSDET_F32 = 1 };
 enum { GLSDET_ACT_NONE = 0, GLSDET_ACT_SILU = 1, GLSDET_ACT_RELU = 2, GLSDET_ACT_LRELU = 3,
@@ -437,6 +437,40 @@ int glsdet_gfl_detect(const glsdet_view* cls, const glsdet_view* reg, int32_t n_
                       float score_thr, int32_t nms_pre, float iou_thr, int32_t max_cand, int32_t max_det,
                       float* dets, int32_t* count, int32_t* status,
                       void* ws, int64_t ws_bytes, void* stream);
+/* ABI 16: the reference's get_bboxes(..., rescale=False, with_nms=False) -- glsdet_gfl_detect up to and including the
+ * level concatenation, without the division by the scale factors and without the NMS.
+ *   cand       : fp32 [n][cap][8] = x1,y1,x2,y2,score,label,0,0, 16-byte aligned.  Rows are level-major and inside a level
+ *                by descending score, ties by lower position*nc+class first: the order of torch.cat(mlvl_*).  Rows at and
+ *                beyond the count are not written.
+ *   cap        : >= sum over levels of min(nms_pre, H_l*W_l*nc)
+ *   cand_count : int32 [n];  status bit0 as in glsdet_gfl_detect
+ *   ws         : glsdet_gfl_candidates_workspace_bytes(n, n_levels, max_cand) bytes, 256-byte aligned                      */
+int64_t glsdet_gfl_candidates_workspace_bytes(int32_t n, int32_t n_levels, int32_t max_cand);
+int glsdet_gfl_candidates(const glsdet_view* cls, const glsdet_view* reg, int32_t n_levels,
+                          const int32_t* strides /*host*/, int32_t num_classes, int32_t reg_max,
+                          int32_t in_h, int32_t in_w, const float* img_hw, float score_thr, int32_t nms_pre,
+                          int32_t max_cand, float* cand, int32_t cap, int32_t* cand_count, int32_t* status,
+                          void* ws, int64_t ws_bytes, void* stream);
+
+/* ABI 16: test-time augmentation, the cross-augmentation step of BBoxTestMixin.aug_test_bboxes
+ * (dense_heads/dense_test_mixins.py:41-114): merge_aug_bboxes (:179-206) with bbox_mapping_back
+ * (core/bbox/transforms.py:22-72), one per-class NMS over the union, the first max_det.
+ *   cands / cand_counts / caps : host arrays of n_augs entries (1 <= n_augs <= GLSDET_MAX_AUGS), read when the call is made
+ *                (or recorded) and carried in the kernel arguments: device rows [n][cap_k][8] as glsdet_gfl_candidates
+ *                writes them, device int32 counts [n], capacities.  The capacities may sum to 32768 at the most.
+ *   aug_meta : device fp32 [n_augs][n][8] = img_h, img_w, sf0, sf1, sf2, sf3, flip code (0 none, 1 horizontal, 2 vertical,
+ *              3 diagonal), 0.  Horizontal: x1' = img_w - x2, x2' = img_w - x1; vertical likewise with img_h; then every
+ *              coordinate is divided by its scale factor -- one fp32 operation each.
+ *   The lists are concatenated in augmentation order; greedy per-class NMS in (score descending, concatenation index
+ *   ascending) order, IoU > iou_thr suppresses, areas without +1; the first max_det; the four coordinates are then
+ *   multiplied by out_scale (device fp32 [n][4]) unless it is NULL (`rescale=False`, dense_test_mixins.py:108-110).
+ *   dets / count / status as glsdet_gfl_detect;  ws: glsdet_aug_merge_workspace_bytes(n, caps, n_augs), 256-byte aligned.  */
+#define GLSDET_MAX_AUGS 12
+int64_t glsdet_aug_merge_workspace_bytes(int32_t n, const int32_t* caps /*host*/, int32_t n_augs);
+int glsdet_aug_merge_nms(const float* const* cands /*host*/, const int32_t* const* cand_counts /*host*/,
+                         const int32_t* caps /*host*/, int32_t n_augs, int32_t n, const float* aug_meta, float iou_thr,
+                         int32_t max_det, const float* out_scale, float* dets, int32_t* count, int32_t* status,
+                         void* ws, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Image preprocessing, drone flavour:
@@ -478,6 +512,16 @@ int glsdet_resize_normalize_pad(const float* src, int32_t h, int32_t w, int32_t 
 int glsdet_resize_normalize_pad_u8(const unsigned char* src, int32_t h, int32_t w, int32_t nh, int32_t nw, float* dst,
                                    int32_t ph, int32_t pw, const double* mean_rgb, const double* std_rgb,
                                    void* stream);
+/* ABI 16: the two calls above followed by mmcv.imflip of the resized nh x nw picture (RandomFlip runs between Resize and
+ * Normalize / Pad, transforms.py:457-461).  flip: 0 none (= the calls above), 1 horizontal, 2 vertical, 3 diagonal.
+ * Destination pixel (y, x) inside nh x nw holds what the unflipped call writes at (nh-1-y if vertical, nw-1-x if
+ * horizontal); the zero padding stays at the right and the bottom.                                                       */
+int glsdet_resize_normalize_pad_ex(const float* src, int32_t h, int32_t w, int32_t nh, int32_t nw, float* dst,
+                                   int32_t ph, int32_t pw, const double* mean_rgb, const double* std_rgb, int32_t flip,
+                                   void* stream);
+int glsdet_resize_normalize_pad_u8_ex(const unsigned char* src, int32_t h, int32_t w, int32_t nh, int32_t nw, float* dst,
+                                      int32_t ph, int32_t pw, const double* mean_rgb, const double* std_rgb, int32_t flip,
+                                      void* stream);
 /* back-mapping + merge NMS (:282-300): dets = the fine detector's rows [max_det][7] (x1,y1,x2,y2,
  * score,score,label) with their count on the device; a row inside a chip's mosaic rectangle (IoF >
  * iof_thr) is mapped to source-image coordinates; per class greedy NMS with '+1' areas, a box
