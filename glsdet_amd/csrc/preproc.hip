@@ -4,7 +4,9 @@
 // Pillow resamples in two passes (horizontal, then vertical) with 8-bit intermediate storage and
 // fixed-point coefficients (22 fractional bits, rounded half away from zero); both passes here
 // use exactly that arithmetic on coefficient tables the host computes the way Pillow's
-// precompute_coeffs / normalize_coeffs_8bpc do, so the result is bit-identical to PIL's.
+// precompute_coeffs / normalize_coeffs_8bpc do, so the result is bit-identical to PIL's wherever PIL keeps
+// that order (Image.resize goes vertically first when in_h > 100 * in_w and the height shrinks; the host
+// refuses such frames, glsdet_amd/preprocess.py: pil_pass_order).
 #include "common.h"
 
 namespace glsdet {

@@ -12,8 +12,10 @@ struct LinTap {
   int i0, i1, c0, c1;      // source indices and 11-bit coefficients
 };
 
-// OpenCV per-axis INTER_LINEAR setup (fraction in float32, taps clamped at the borders)
+// OpenCV per-axis INTER_LINEAR setup (fraction in float32, taps clamped at the borders).  OpenCV's scalar set-up
+// code rounds the product and the difference separately: no fused multiply-add here.
 __device__ __forceinline__ void lin_tap_f(int d, int dst, int src, int& i0, int& i1, float& f) {
+#pragma clang fp contract(off)
   const double scale = 1.0 / ((double)dst / (double)src);
   float fx = (float)(((double)d + 0.5) * scale - 0.5);
   int s = (int)floorf(fx);
@@ -91,6 +93,7 @@ __global__ __launch_bounds__(256) void resize_norm_pad_kernel(const float* __res
       lin_tap_f(ys, nh, h, y0, y1, fy);
 #pragma unroll
       for (int e = 0; e < 3; ++e) {
+#pragma clang fp contract(off)                                    // every product and sum rounded on its own, as numpy does
         const double a = (double)src[((long)y0 * w + x0) * 3 + e] * (1.0 - (double)fx) + (double)src[((long)y0 * w + x1) * 3 + e] * (double)fx;
         const double b = (double)src[((long)y1 * w + x0) * 3 + e] * (1.0 - (double)fx) + (double)src[((long)y1 * w + x1) * 3 + e] * (double)fx;
         const float bgr = (float)(a * (1.0 - (double)fy) + b * (double)fy);

@@ -1,7 +1,9 @@
 """Device-side image preprocessing of the drone flavour:
 `resize_image` (PIL BICUBIC, optional letterbox on a gray canvas) + `preprocess_input` + HWC->CHW
 (drone/models/core/utils.py:21-34,46-50; drone/yolo.py:125-134), bit-identical to the reference's
-CPU result.  Host side here = the coefficient tables Pillow's resampler would compute; the two
+CPU result wherever Pillow resamples horizontally first: every frame except those more than a hundred
+times as high as wide whose height shrinks (`pil_pass_order`); such a frame is refused, not resampled
+in the other order.  Host side here = the coefficient tables Pillow's resampler would compute; the two
 resampling passes, the normalisation and the layout change run in libglsdet_hip
 (glsdet_pil_resize_normalize)."""
 from __future__ import annotations
@@ -54,6 +56,14 @@ def pil_bicubic_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndar
     return bounds, kk, ksize
 
 
+def pil_pass_order(in_hw: Sequence[int], out_hw: Sequence[int]) -> str:
+    """The order of Pillow's two resampling passes for a whole-image `Image.resize` from in_hw = (h, w) to out_hw:
+    'hv' (horizontal, then vertical: the C resampler's own order) or 'vh'.  `Image.resize` (Pillow 12.2, PIL/Image.py)
+    runs the vertical pass first when `in_h > 100 * in_w and out_h < in_h`, to keep the intermediate picture small.
+    Both passes round to uint8, so the two orders give different pixels; the device kernels implement 'hv' alone."""
+    return "vh" if int(in_hw[0]) > 100 * int(in_hw[1]) and int(out_hw[0]) < int(in_hw[0]) else "hv"
+
+
 class DronePreprocessor:
     """images (uint8 HWC RGB, any sizes) -> float32 [B,3,H,W] on the GPU, as yolo.py:125-134 does on the
     CPU for one image.  Tables are cached per (in, out) size."""
@@ -99,6 +109,10 @@ class DronePreprocessor:
                 ox, oy = (W - nw) // 2, (H - nh) // 2
             else:
                 nw, nh, ox, oy = W, H, 0, 0
+            if pil_pass_order((ih, iw), (nh, nw)) != "hv":
+                raise ValueError("a %dx%d frame resized to %dx%d: Pillow resamples vertically first when in_h > 100 * in_w and "
+                                 "the height shrinks, the device kernels horizontally first; the result would not be Pillow's"
+                                 % (ih, iw, nh, nw))
             xb, xk, xks = self._table(iw, nw)
             yb, yk, yks = self._table(ih, nh)
             tmp = torch.empty(ih * nw * 3, dtype=torch.uint8, device=self.device)

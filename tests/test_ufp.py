@@ -133,7 +133,7 @@ def test_hip_pipeline_input_vs_restatement():
     got, m = UfpSecondStage().pipeline_input(torch.from_numpy(canvas.astype(np.float32)).cuda())
     assert tuple(got.shape) == want.shape and m["img_shape"] == meta["img_shape"] and m["pad_shape"] == meta["pad_shape"]
     assert np.array_equal(m["scale_factor"], meta["scale_factor"])
-    assert np.abs(got.cpu().numpy() - want).max() <= 1e-5
+    assert np.array_equal(got.cpu().numpy(), want)               # the same float64 operations, unfused: exact
     assert got.shape[2] % 32 == 0 and got.shape[3] % 32 == 0 and max(m["img_shape"][:2]) <= 1333
 
 
