@@ -1064,6 +1064,36 @@ class Engine:
               "aug_merge_nms")
         return mb["dets"], mb["count"], mb["status"]
 
+    SOFT_NMS_METHODS = {"linear": 1, "gaussian": 2, "hard": 3}
+
+    def soft_nms_buffers(self, n: int, cap: int, max_det: int):
+        nbytes = self.lib.glsdet_soft_nms_workspace_bytes(n, cap)
+        if nbytes <= 0 or max_det < 1:
+            raise _lib.GlsdetError("soft_nms: n %d, cap %d, max_det %d; need n >= 1, 1 <= cap <= 32768, max_det >= 1"
+                                   % (n, cap, max_det))
+        return {"ws": self.raw(nbytes), "n": n, "cap": cap, "max_det": max_det,
+                "segment_limit": int(self.lib.glsdet_soft_nms_segment_limit()),
+                "dets": torch.zeros(n, max_det, 7, dtype=torch.float32, device=self.device),
+                "count": torch.zeros(2 * n, dtype=torch.int32, device=self.device),
+                "status": torch.zeros(1, dtype=torch.int32, device=self.device)}
+
+    def soft_nms(self, cand: torch.Tensor, counts: torch.Tensor, num_classes: int, sb, method: str = "gaussian",
+                 iou_thr: float = 0.3, sigma: float = 0.5, min_score: float = 1e-4, rescore: bool = False):
+        """glsdet_soft_nms (drone/merge_results.py:41-130) over candidate rows [n, cap, 8] fp32 + int32 [n] counts into sb
+        (soft_nms_buffers): dets rows x1,y1,x2,y2, original score, decayed score, label in descending original score
+        (rescore: decayed score).  status bit0: a count above cap, bit1: a class segment above sb["segment_limit"] or a
+        label outside [0, num_classes) -- the caller raises on either."""
+        if method not in self.SOFT_NMS_METHODS:
+            raise ValueError("soft_nms: method %r is not one of %s" % (method, sorted(self.SOFT_NMS_METHODS)))
+        n, cap = sb["n"], sb["cap"]
+        assert cand.dtype == torch.float32 and cand.is_contiguous() and tuple(cand.shape) == (n, cap, 8)
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == n
+        check(self.lib.glsdet_soft_nms(cand.data_ptr(), counts.data_ptr(), n, cap, num_classes, self.SOFT_NMS_METHODS[method],
+                                       iou_thr, sigma, min_score, int(bool(rescore)), sb["max_det"], sb["dets"].data_ptr(),
+                                       sb["count"].data_ptr(), sb["status"].data_ptr(), sb["ws"].data_ptr(), sb["ws"].numel(),
+                                       _stream_ptr(self.stream)), "soft_nms")
+        return sb["dets"], sb["count"], sb["status"]
+
     def branch(self, b: int):
         """Ops emitted until the next branch(0) belong to independent branch b (1..8): quadrant
         convs, the l/r/t/b stitch convs, the cls/reg towers.  No-op outside plan recording."""

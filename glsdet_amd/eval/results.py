@@ -4,10 +4,12 @@
                                       parsers: ufp/myufp_eval.py:27-76, drone/merge_results.py:20-39
     COCO result records               ufp/ufpmp_det_eval.py:303-326  (int-truncated corners -> xywh)
     merge of two result directories   drone/merge_results.py:132-172 (concatenate, batched_nms 0.65, rewrite)
+    the same with the soft rule       drone/merge_results.py:41-130 + the call of :159-163 (commented out in the reference)
 
 The merge NMS runs on the GPU through `glsdet_nms` (class-aware greedy NMS, IoU > thr suppresses, areas
 without +1 -- torchvision.ops.boxes.batched_nms).  The lossy steps of the reference are kept: the score
-STRING cut to 6 characters, coordinates through int()."""
+STRING cut to 6 characters, coordinates through int().  ResultMerger(method="soft") takes the reference's other rule,
+`batched_soft_nms` over `py_cpu_softnms`, through `glsdet_soft_nms`."""
 from __future__ import annotations
 
 import os
@@ -82,17 +84,70 @@ def coco_records(image_id, per_class: Sequence[np.ndarray]) -> List[dict]:
 
 # ------------------------------------------------------------------------------------ merging result files
 class ResultMerger:
-    """drone/merge_results.py:132-172 for one image at a time, NMS on the device."""
+    """drone/merge_results.py:132-172 for one image at a time, NMS on the device.
+
+    method="hard" (default): `boxes.batched_nms(..., nms_thres)`, :153-158, through glsdet_nms.
+    method="soft": the call the reference ships commented out, `batched_soft_nms` (:121-130, :159-163) through
+    glsdet_soft_nms: per class `py_cpu_softnms` (:41-119) with soft_method "gaussian" | "linear" | "hard", `iou_thr` (Nt),
+    `sigma` and `min_score` (thresh) -- the defaults are the reference's 0.3 / 0.5 / 1e-4 -- and the kept rows in
+    descending ORIGINAL score, which is also the score written to the file (the reference decays a copy).
+    rescore=True sorts by and writes the decayed score instead; that is this project's addition, the reference has no
+    such switch.  nms_thres is not used by the soft rule."""
+
+    SOFT_METHODS = ("gaussian", "linear", "hard")
 
     def __init__(self, classes: Sequence[str] = VISDRONE_CLASSES, nms_thres: float = 0.65, device: str = "cuda:0",
-                 capacity: int = 8192):
+                 capacity: int = 8192, method: str = "hard", soft_method: str = "gaussian", sigma: float = 0.5,
+                 iou_thr: float = 0.3, min_score: float = 1e-4, rescore: bool = False):
+        if method not in ("hard", "soft"):
+            raise ValueError("ResultMerger: method %r is not 'hard' or 'soft'" % (method,))
+        if method == "soft":
+            if soft_method not in self.SOFT_METHODS:
+                raise ValueError("ResultMerger: soft_method %r is not one of %s" % (soft_method, self.SOFT_METHODS))
+            if soft_method == "gaussian" and not float(sigma) > 0:
+                raise ValueError("ResultMerger: the gaussian decay needs sigma > 0 (got %r)" % (sigma,))
+            if float(iou_thr) != float(iou_thr):
+                raise ValueError("ResultMerger: iou_thr is NaN")
+            if not 0 <= float(min_score) < float("inf"):
+                raise ValueError("ResultMerger: min_score must be finite and >= 0 (got %r)" % (min_score,))
+            if not 1 <= int(capacity) <= 32768:
+                raise ValueError("ResultMerger: the soft rule takes a capacity of 1 .. 32768 rows (got %r)" % (capacity,))
+        elif rescore:
+            raise ValueError("ResultMerger: rescore=True needs method='soft'")
         from ..engine import Engine
         self.classes = tuple(classes)
         self.index = {c: i for i, c in enumerate(self.classes)}
         self.thr, self.cap = float(nms_thres), int(capacity)
+        self.method, self.soft_method, self.rescore = method, soft_method, bool(rescore)
+        self.sigma, self.iou_thr, self.min_score = float(sigma), float(iou_thr), float(min_score)
         self.eng = Engine(device=device, dtype="f32")
+        if method == "soft":
+            self._sb = self.eng.soft_nms_buffers(1, self.cap, self.cap)
+            self._cand = torch.zeros(1, self.cap, 8, dtype=torch.float32, device=self.eng.device)
+            self._cnt = torch.zeros(1, dtype=torch.int32, device=self.eng.device)
+            return
         self._nb = self.eng.nms_buffers(1, self.cap, self.cap, self.cap)
         self._pred = torch.zeros(1, self.cap, 5 + len(self.classes), dtype=torch.float32, device=self.eng.device)
+
+    def _merge_rows_soft(self, rows: np.ndarray) -> np.ndarray:
+        n = len(rows)
+        if not (np.isfinite(rows[:, 4]).all() and (rows[:, 4] >= 0).all()):
+            raise RuntimeError("soft merge: scores must be finite and >= 0")
+        host = np.zeros((self.cap, 8), np.float32)
+        host[:n, :6] = rows
+        self._cand[0].copy_(torch.from_numpy(host))
+        self._cnt.fill_(n)
+        dets, count, status = self.eng.soft_nms(self._cand, self._cnt, len(self.classes), self._sb, self.soft_method,
+                                                self.iou_thr, self.sigma, self.min_score, self.rescore)
+        torch.cuda.current_stream(self.eng.device).synchronize()
+        st = int(status.item())
+        if st & 1:
+            raise RuntimeError("soft merge: more rows than the candidate capacity %d" % self.cap)
+        if st & 2:
+            raise RuntimeError("soft merge: a class holds more than %d rows, or a class index lies outside [0, %d)"
+                               % (self._sb["segment_limit"], len(self.classes)))
+        d = dets[0, : int(count[0].item())].cpu().numpy()
+        return np.concatenate([d[:, :4], d[:, 5:6] if self.rescore else d[:, 4:5], d[:, 6:7]], axis=1)
 
     def merge_rows(self, rows: np.ndarray) -> np.ndarray:
         """rows [n,6] left, top, right, bottom, score, class -> the kept rows in descending score order."""
@@ -102,6 +157,8 @@ class ResultMerger:
             return rows
         if n > self.cap:
             raise RuntimeError("more rows (%d) than the merger's capacity %d" % (n, self.cap))
+        if self.method == "soft":
+            return self._merge_rows_soft(rows)
         # obj = 1 and the class scores are -1 everywhere except the row's own class: the class max is then the row's
         # score at the row's class also for a score of exactly 0 (a '0.0000' cut of the reference's 6-character score
         # string, which merge_results.py keeps), and the all -1 padding rows fall under the threshold of -0.5

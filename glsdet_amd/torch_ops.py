@@ -16,6 +16,10 @@ allocated by the op on the input's device, nothing synchronises.  There is no CP
         objectness, bit 1 classes, channels outside the mask stay raw logits (the variants of utils_bbox.py:36-253)
     glsdet::nms(pred, num_classes, box_mode, conf_thres, nms_thres, max_det) -> (dets [N,max_det,7], count [2N], status [1])
         class max + threshold + per-class NMS of non_max_suppression, utils_bbox.py:375-419
+    glsdet::soft_nms(cand, counts, num_classes, method, iou_thr, sigma, min_score, rescore, max_det)
+            -> (dets [N,max_det,7], count [2N], status [1])
+        py_cpu_softnms / batched_soft_nms, drone/merge_results.py:41-130; cand fp32 [N, cap, 8] rows x1,y1,x2,y2,score,label,
+        counts int32 [N]; method 1 linear, 2 gaussian, 3 hard; dets rows x1,y1,x2,y2, original score, decayed score, label
     glsdet::batched_nms(boxes, scores, idxs, iou_threshold) -> keep int64 [K]
         torchvision.ops.boxes.batched_nms's signature (utils_bbox.py:414-419), one image
 
@@ -91,6 +95,8 @@ def register():
     lib_def.define("yolox_decode(Tensor[] levels, int num_classes, int in_h, int in_w, int mode=0, int sigmoid=3) -> Tensor")
     lib_def.define("nms(Tensor pred, int num_classes, int box_mode, float conf_thres, float nms_thres, int max_det) -> "
                    "(Tensor, Tensor, Tensor)")
+    lib_def.define("soft_nms(Tensor cand, Tensor counts, int num_classes, int method, float iou_thr, float sigma, "
+                   "float min_score, bool rescore, int max_det) -> (Tensor, Tensor, Tensor)")
     lib_def.define("batched_nms(Tensor boxes, Tensor scores, Tensor idxs, float iou_threshold) -> Tensor")
     impl = torch.library.Library("glsdet", "IMPL", "CUDA")
     cpu = torch.library.Library("glsdet", "IMPL", "CPU")
@@ -177,6 +183,29 @@ def register():
         return (pred.new_empty((n, max_det, 7)), pred.new_empty((2 * n,), dtype=torch.int32),
                 pred.new_empty((1,), dtype=torch.int32))
 
+    # ------------------------------------------------------------------ soft_nms
+    def soft_nms(cand, counts, num_classes, method, iou_thr, sigma, min_score, rescore, max_det):
+        lib = _lib.load()
+        _need_cuda(cand, counts)
+        if cand.dtype != torch.float32 or not cand.is_contiguous() or cand.dim() != 3 or cand.shape[2] != 8:
+            raise RuntimeError("soft_nms: cand must be a contiguous fp32 [N, cap, 8] tensor")
+        n, cap = cand.shape[0], cand.shape[1]
+        if counts.dtype != torch.int32 or not counts.is_contiguous() or counts.numel() != n:
+            raise RuntimeError("soft_nms: counts must be a contiguous int32 [N] tensor")
+        ws = torch.empty(max(int(lib.glsdet_soft_nms_workspace_bytes(n, cap)), 256), dtype=torch.uint8, device=cand.device)
+        dets = torch.zeros(n, max_det, 7, dtype=torch.float32, device=cand.device)
+        count = torch.zeros(2 * n, dtype=torch.int32, device=cand.device)
+        status = torch.zeros(1, dtype=torch.int32, device=cand.device)
+        check(lib.glsdet_soft_nms(cand.data_ptr(), counts.data_ptr(), n, cap, num_classes, method, iou_thr, sigma, min_score,
+                                  int(rescore), max_det, dets.data_ptr(), count.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                  ws.numel(), _stream(cand)), "soft_nms")
+        return dets, count, status
+
+    def soft_nms_meta(cand, counts, num_classes, method, iou_thr, sigma, min_score, rescore, max_det):
+        n = cand.shape[0]
+        return (cand.new_empty((n, max_det, 7)), cand.new_empty((2 * n,), dtype=torch.int32),
+                cand.new_empty((1,), dtype=torch.int32))
+
     # ------------------------------------------------------------------ batched_nms (torchvision's signature)
     def batched_nms(boxes, scores, idxs, iou_threshold):
         _need_cuda(boxes, scores, idxs)
@@ -201,6 +230,7 @@ def register():
 
     for name, fn, fm in (("conv_bn_act", conv_bn_act, conv_bn_act_meta), ("nonlocal_dot", nonlocal_dot, lambda x, *a: torch.empty_like(x)),
                          ("yolox_decode", yolox_decode, yolox_decode_meta), ("nms", nms, nms_meta),
+                         ("soft_nms", soft_nms, soft_nms_meta),
                          ("batched_nms", batched_nms, lambda b, s, i, t: b.new_empty((0,), dtype=torch.int64))):
         impl.impl(name, fn)
         cpu.impl(name, no_cpu)

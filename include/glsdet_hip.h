@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GLSDET_ABI_VERSION 16
+#define GLSDET_ABI_VERSION 17
 
 enum { GLSDET_F16 = 0, GLSDET_F32 = 1 };
 enum { GLSDET_ACT_NONE = 0, GLSDET_ACT_SILU = 1, GLSDET_ACT_RELU = 2, GLSDET_ACT_LRELU = 3,
@@ -471,6 +471,46 @@ int glsdet_aug_merge_nms(const float* const* cands /*host*/, const int32_t* cons
                          const int32_t* caps /*host*/, int32_t n_augs, int32_t n, const float* aug_meta, float iou_thr,
                          int32_t max_det, const float* out_scale, float* dets, int32_t* count, int32_t* status,
                          void* ws, int64_t ws_bytes, void* stream);
+
+/* ABI 17: Soft-NMS of merged result rows, drone/merge_results.py:41-130 (py_cpu_softnms, batched_soft_nms) with the call
+ * of :159-163 taken (the reference ships with that call commented out and batched_nms live).
+ *   cand / cand_count : the candidate rows of glsdet_gfl_candidates: fp32 [n][cap][8] = x1,y1,x2,y2,score,label,(2 columns
+ *              that are not read), 16-byte aligned, and int32 [n] counts on the device; a count is clamped to [0, cap]
+ *              before any loop uses it.  cap <= 32768.  Scores must be finite and >= 0, boxes x2 >= x1 and y2 >= y1,
+ *              labels integer-valued.
+ *   Per image and per class present, the class's rows in ascending original index form a segment of N positions
+ *   (box, score, original index), and for i = 0 .. N-1:
+ *     selection : if i != N-1, m = the FIRST position of the maximum of score[i+1:]; if score[i] < score[m] (strict: a tie
+ *                 leaves the order alone) positions i and m are SWAPPED (box, score, index -- a swap, not a rotation).
+ *     overlap   : for every k > i, in fp64 on the fp32 coordinates, every operation rounded on its own:
+ *                 w = max(0, min(x2) - max(x1) + 1), h alike, inter = w * h, ovr = inter / (area_i + area_k - inter),
+ *                 area = (x2 - x1 + 1) * (y2 - y1 + 1).
+ *     weight    : method 1 (linear)   1 - ovr if ovr > iou_thr, else 1
+ *                 method 2 (gaussian) exp(-(ovr * ovr) / sigma), fp64
+ *                 method 3 (hard)     0 if ovr > iou_thr, else 1
+ *     update    : score[k] = fp32(weight * fp64(score[k])), one rounding to fp32 per update.
+ *   A row survives when its decayed score > min_score (strict, compared in fp32).  The reference's values are
+ *   iou_thr (Nt) 0.3, sigma 0.5, min_score (thresh) 1e-4, method 2.  iou_thr and sigma are doubles because the
+ *   reference compares and divides in fp64.  The loop stops once the largest remaining score is <= min_score: weights lie
+ *   in [0, 1] and scores are >= 0, so nothing behind that point can survive.
+ *   The survivors of an image are sorted by ORIGINAL score descending (batched_soft_nms: the decay works on a copy), with
+ *   rescore != 0 by decayed score descending; ties go to the lower original index (the reference's torch.sort leaves them
+ *   unspecified).  The first max_det are written.
+ *   dets   : fp32 [n][max_det][7] = x1,y1,x2,y2, original score, decayed score, label; rows at and beyond the count are
+ *            not written.   count: int32 [2n], survivors clamped to max_det, then unclamped.
+ *   status : int32 [1]; bit0: a count exceeds cap; bit1: a class segment is longer than
+ *            glsdet_soft_nms_segment_limit() or a label lies outside [0, num_classes).  With either bit set the results
+ *            are invalid (every loop stays clamped; rows of an over-long segment or with a bad label are dropped).
+ *   glsdet_soft_nms_segment_limit() = 6784: a segment stays in LDS as fp32 box (16 bytes) + fp32 score + int32 index
+ *            = 24 bytes per row behind 1024 bytes of reduction slots; (160 KiB - 1 KiB) / 24 = 6784.
+ *   ws     : glsdet_soft_nms_workspace_bytes(n, cap) bytes, 256-byte aligned (0 for n < 1 or cap outside 1 .. 32768).
+ *   Refused on the host: n < 1, cap > 32768, method outside 1..3, sigma <= 0 with method 2, min_score negative or not
+ *   finite (dropped rows carry a decayed score of 0, which must not pass), misaligned buffers, a short workspace.                                                                                                           */
+int64_t glsdet_soft_nms_workspace_bytes(int32_t n, int32_t cap);
+int32_t glsdet_soft_nms_segment_limit(void);
+int glsdet_soft_nms(const float* cand, const int32_t* cand_count, int32_t n, int32_t cap, int32_t num_classes,
+                    int32_t method, double iou_thr, double sigma, float min_score, int32_t rescore, int32_t max_det,
+                    float* dets, int32_t* count, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Image preprocessing, drone flavour:
