@@ -18,6 +18,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "conv_common.h"
@@ -482,11 +483,7 @@ static int launch_conv(const ConvArgs& a, hipStream_t st) {
     attr_lds = want_attr;
   }
   ConvArgs b = a;
-  b.n_co_tiles = (a.cout_pad + CO_T - 1) / CO_T;
-  // tiles that would only cover the zero padding of cout_pad are never created
-  if ((b.n_co_tiles - 1) * CO_T >= a.Cout) b.n_co_tiles = (a.Cout + CO_T - 1) / CO_T;
-  gls_fastdiv(b.n_co_tiles, &b.nco_mul, &b.nco_sh);
-  b.n_px_tiles = (a.M + PX_T - 1) / PX_T;
+  fill_flat_tiles<CO_T, PX_T>(b);
   const long grid = (long)b.n_co_tiles * b.n_px_tiles;
   if (grid <= 0 || grid > 0x7fffffffL) GLS_FAIL(GLSDET_E_ARG, "conv2d: grid %ld out of range", grid);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NTHR), lds, st, b);
@@ -495,7 +492,7 @@ static int launch_conv(const ConvArgs& a, hipStream_t st) {
 }
 
 template <typename T, typename TO, int CO_T, int PX_T, int KB, int WCO, bool UT>
-static int launch_conv_multi(const ConvArgsN& m0, hipStream_t st) {
+static int launch_conv(const ConvArgsN& m0, hipStream_t st) {
   bool any_res = false;
   for (int i = 0; i < m0.n; ++i) any_res = any_res || m0.p[i].res != nullptr;
   const int lds = conv_lds_bytes<CO_T, PX_T, KB, TO>(any_res);
@@ -510,10 +507,7 @@ static int launch_conv_multi(const ConvArgsN& m0, hipStream_t st) {
   long grid = 0;
   for (int i = 0; i < m.n; ++i) {
     ConvArgs& b = m.p[i];
-    b.n_co_tiles = (b.cout_pad + CO_T - 1) / CO_T;
-    if ((b.n_co_tiles - 1) * CO_T >= b.Cout) b.n_co_tiles = (b.Cout + CO_T - 1) / CO_T;
-    gls_fastdiv(b.n_co_tiles, &b.nco_mul, &b.nco_sh);
-    b.n_px_tiles = (b.M + PX_T - 1) / PX_T;
+    fill_flat_tiles<CO_T, PX_T>(b);
     m.start[i] = (int)grid;
     grid += (long)b.n_co_tiles * b.n_px_tiles;
   }
@@ -525,7 +519,7 @@ static int launch_conv_multi(const ConvArgsN& m0, hipStream_t st) {
 }
 
 template <typename T, typename TO, int CO_T, int PX_T, int KB, int WCO, bool UT>
-static int launch_conv_batch(const ConvArgsB& m0, hipStream_t st) {
+static int launch_conv(const ConvArgsB& m0, hipStream_t st) {
   const int lds = conv_lds_bytes<CO_T, PX_T, KB, TO>(m0.base.res != nullptr);
   static bool attr_set = false;
   auto kern = conv_igemm_batch_kernel<T, TO, CO_T, PX_T, KB, WCO, UT>;
@@ -536,10 +530,7 @@ static int launch_conv_batch(const ConvArgsB& m0, hipStream_t st) {
   }
   ConvArgsB m = m0;
   ConvArgs& b = m.base;
-  b.n_co_tiles = (b.cout_pad + CO_T - 1) / CO_T;
-  if ((b.n_co_tiles - 1) * CO_T >= b.Cout) b.n_co_tiles = (b.Cout + CO_T - 1) / CO_T;
-  gls_fastdiv(b.n_co_tiles, &b.nco_mul, &b.nco_sh);
-  b.n_px_tiles = (b.M + PX_T - 1) / PX_T;
+  fill_flat_tiles<CO_T, PX_T>(b);
   m.tiles = b.n_co_tiles * b.n_px_tiles;
   gls_fastdiv(m.tiles, &m.tiles_mul, &m.tiles_sh);
   const long grid = (long)m.tiles * m.n;
@@ -549,68 +540,58 @@ static int launch_conv_batch(const ConvArgsB& m0, hipStream_t st) {
   return 0;
 }
 
-template <typename T, typename TO>
-static int dispatch_tile_batch(const ConvArgsB& m, int co_t, int px_t, int kb, hipStream_t st) {
-  const bool ut = ((long)m.base.Cin * (long)sizeof(T)) % kb == 0;
-#define GLS_CASE(CO, PX, WCO_)                                                                      \
-  if (co_t == CO && px_t == PX) {                                                                   \
-    if (ut) return kb == 128 ? launch_conv_batch<T, TO, CO, PX, 128, WCO_, true>(m, st)             \
-                             : launch_conv_batch<T, TO, CO, PX, 64, WCO_, true>(m, st);             \
-    return kb == 128 ? launch_conv_batch<T, TO, CO, PX, 128, WCO_, false>(m, st)                    \
-                     : launch_conv_batch<T, TO, CO, PX, 64, WCO_, false>(m, st);                    \
+// The tiles the generic kernel is compiled for: f(CO_T, PX_T, WCO, NTHR) as integral constants, or NO_TILE.
+// SINGLE (glsdet_conv2d / _chain) has two tiles more than the grouped and batched forms: 32 x 128, and the eight-wave
+// 128 x 256 (64 x 64 per wave).
+constexpr int NO_TILE = 1;      // (no error code: those are negative)
+template <bool SINGLE, typename F>
+static int with_tile(int co_t, int px_t, F&& f) {
+  if (co_t == 128 && px_t == 128) return f(IC<128>{}, IC<128>{}, IC<2>{}, IC<256>{});
+  if (co_t == 64 && px_t == 128) return f(IC<64>{}, IC<128>{}, IC<2>{}, IC<256>{});
+  if (co_t == 64 && px_t == 64) return f(IC<64>{}, IC<64>{}, IC<2>{}, IC<256>{});
+  if constexpr (SINGLE) {
+    if (co_t == 32 && px_t == 128) return f(IC<32>{}, IC<128>{}, IC<1>{}, IC<256>{});
+    if (co_t == 128 && px_t == 256) return f(IC<128>{}, IC<256>{}, IC<2>{}, IC<512>{});
   }
-  GLS_CASE(128, 128, 2)
-  GLS_CASE(64, 128, 2)
-  GLS_CASE(64, 64, 2)
-#undef GLS_CASE
-  GLS_FAIL(GLSDET_E_ARG, "conv2d_multi: no kernel for tile %dx%d", co_t, px_t);
+  return NO_TILE;
+}
+template <bool SINGLE>
+static bool tile_compiled(int co_t, int px_t) {
+  return with_tile<SINGLE>(co_t, px_t, [](auto, auto, auto, auto) { return 0; }) == 0;
+}
+static const ConvArgs& first_problem(const ConvArgs& a) { return a; }
+static const ConvArgs& first_problem(const ConvArgsN& m) { return m.p[0]; }
+static const ConvArgs& first_problem(const ConvArgsB& m) { return m.base; }
+
+// one dispatch over (tile, K step, uniform tap) for the three argument blocks: ConvArgs, ConvArgsN (grouped), ConvArgsB (batched)
+template <typename T, typename TO, typename Args>
+static int dispatch_tile(const Args& m, int co_t, int px_t, int kb, hipStream_t st) {
+  constexpr bool SINGLE = std::is_same<Args, ConvArgs>::value;
+  static const bool no_ut = SINGLE && getenv("GLSDET_NO_UT") != nullptr;   // A/B switch for measurements (glsdet_conv2d only)
+  const bool ut = !no_ut && ((long)first_problem(m).Cin * (long)sizeof(T)) % kb == 0;     // every K step inside one filter tap
+  const int rc = with_tile<SINGLE>(co_t, px_t, [&](auto co, auto px, auto wco, auto nthr) -> int {
+    auto go = [&](auto kbc, auto utc) -> int {
+      constexpr int CO = decltype(co)::value, PX = decltype(px)::value, KB = decltype(kbc)::value, WCO = decltype(wco)::value;
+      constexpr bool UT = decltype(utc)::value;
+      if constexpr (SINGLE) return launch_conv<T, TO, CO, PX, KB, WCO, UT, false, decltype(nthr)::value>(m, st);
+      else return launch_conv<T, TO, CO, PX, KB, WCO, UT>(m, st);
+    };
+    if (ut) return kb == 128 ? go(IC<128>{}, std::true_type{}) : go(IC<64>{}, std::true_type{});
+    if constexpr (decltype(nthr)::value == 512) {          // eight waves (uniform-tap problems only; build_conv_op refuses the others)
+      GLS_FAIL(GLSDET_E_ARG, "conv2d: the 128x256 tile needs Cin to be a whole number of K steps");
+    } else {
+      return kb == 128 ? go(IC<128>{}, std::false_type{}) : go(IC<64>{}, std::false_type{});
+    }
+  });
+  if (rc == NO_TILE) GLS_FAIL(GLSDET_E_ARG, "conv2d: no kernel for tile %dx%d", co_t, px_t);
+  return rc;
 }
 
-template <typename T, typename TO>
-static int dispatch_tile_multi(const ConvArgsN& m, int co_t, int px_t, int kb, hipStream_t st) {
-  const bool ut = ((long)m.p[0].Cin * (long)sizeof(T)) % kb == 0;
-#define GLS_CASE(CO, PX, WCO_)                                                                      \
-  if (co_t == CO && px_t == PX) {                                                                   \
-    if (ut) return kb == 128 ? launch_conv_multi<T, TO, CO, PX, 128, WCO_, true>(m, st)             \
-                             : launch_conv_multi<T, TO, CO, PX, 64, WCO_, true>(m, st);             \
-    return kb == 128 ? launch_conv_multi<T, TO, CO, PX, 128, WCO_, false>(m, st)                    \
-                     : launch_conv_multi<T, TO, CO, PX, 64, WCO_, false>(m, st);                    \
-  }
-  GLS_CASE(128, 128, 2)
-  GLS_CASE(64, 128, 2)
-  GLS_CASE(64, 64, 2)
-#undef GLS_CASE
-  GLS_FAIL(GLSDET_E_ARG, "conv2d_multi: no kernel for tile %dx%d", co_t, px_t);
-}
-
-template <typename T, typename TO>
-static int dispatch_tile(const ConvArgs& a, int co_t, int px_t, int kb, hipStream_t st) {
-  static const bool no_ut = getenv("GLSDET_NO_UT") != nullptr;            // A/B switch for measurements
-  const bool ut = !no_ut && ((long)a.Cin * (long)sizeof(T)) % kb == 0;     // every K step inside one filter tap
-#define GLS_CASE(CO, PX, WCO_)                                                                      \
-  if (co_t == CO && px_t == PX) {                                                                   \
-    if (ut) return kb == 128 ? launch_conv<T, TO, CO, PX, 128, WCO_, true>(a, st)                   \
-                             : launch_conv<T, TO, CO, PX, 64, WCO_, true>(a, st);                   \
-    return kb == 128 ? launch_conv<T, TO, CO, PX, 128, WCO_, false>(a, st)                          \
-                     : launch_conv<T, TO, CO, PX, 64, WCO_, false>(a, st);                          \
-  }
-  GLS_CASE(128, 128, 2)
-  GLS_CASE(64, 128, 2)
-  GLS_CASE(32, 128, 1)
-  GLS_CASE(64, 64, 2)
-#undef GLS_CASE
-  if (co_t == 128 && px_t == 256) {          // eight waves, 64 x 64 each (uniform-tap problems only)
-    if (!ut || a.w2) GLS_FAIL(GLSDET_E_ARG, "conv2d: the 128x256 tile needs Cin to be a whole number of K steps and no chained conv");
-    return kb == 128 ? launch_conv<T, TO, 128, 256, 128, 2, true, false, 512>(a, st) : launch_conv<T, TO, 128, 256, 64, 2, true, false, 512>(a, st);
-  }
-  GLS_FAIL(GLSDET_E_ARG, "conv2d: no kernel for tile %dx%d", co_t, px_t);
-}
-
-static void pick_tile(const ConvArgs& a, int elem, int hint, int* co_t, int* px_t, int* kb) {
-  if (hint) {
-    *co_t = hint >> 16;
-    *px_t = hint & 0xff;
-    if (*px_t == 0) *px_t = 256;        // co<<16 | 0: the eight-wave 128 x 256 tile (bits 8..10 of a tile hint are diagnostic switches)
+// the tile of the generic kernel: the hint's explicit one, else chosen here
+static void pick_tile(const ConvArgs& a, int elem, const TileHint& hint, int* co_t, int* px_t, int* kb) {
+  if (hint.explicit_tile()) {
+    *co_t = hint.co_t;
+    *px_t = hint.px_t;
   } else {
     // largest tile that still gives the chip >= 3 workgroups per CU; below that the layer
     // is latency bound and more, smaller workgroups win over MFMA density
@@ -629,7 +610,7 @@ static void pick_tile(const ConvArgs& a, int elem, int hint, int* co_t, int* px_
     }
   }
   *kb = ((long)a.kreal * elem) % 128 == 0 ? 128 : 64;
-  if (hint & 0x8000) *kb = 64;      // explicit 64-byte K steps: half the LDS / registers -> more workgroups per CU
+  if (hint.explicit_tile() && hint.k64) *kb = 64;      // explicit 64-byte K steps: half the LDS / registers -> more workgroups per CU
 }
 
 }  // namespace glsdet
@@ -647,7 +628,7 @@ extern "C" int64_t glsdet_conv_weight_elems(int32_t cout, int32_t R, int32_t S, 
 }
 
 // validate the descriptor and fill the kernel argument block
-static int make_conv_args(const glsdet_conv_desc* d, int hint, ConvArgs& a, double* flops, double* bytes) {
+static int make_conv_args(const glsdet_conv_desc* d, const TileHint& hint, ConvArgs& a, double* flops, double* bytes) {
   if (!d) GLS_FAIL(GLSDET_E_ARG, "conv2d: null descriptor");
   const glsdet_view &x = d->x, &y = d->y;
   int rc;
@@ -689,7 +670,7 @@ static int make_conv_args(const glsdet_conv_desc* d, int hint, ConvArgs& a, doub
   a.R = d->R; a.S = d->S; a.stride = d->stride; a.pad = d->pad;
   a.act = d->act & 0xff;
   a.act_post = 0;
-  a.dbg = hint >= 0x10000 ? (hint >> 8) & 7 : 0;
+  a.dbg = hint.dbg;
   if ((d->act & GLSDET_ACT_RES_FIRST) && has_res) { a.act_post = a.act; a.act = GLSDET_ACT_NONE; }
   a.kreal = d->R * d->S * x.c;
   a.kpad = glsdet_conv_kpad(d->R, d->S, x.c, x.dtype);
@@ -764,9 +745,19 @@ static bool chain_fits(const ConvArgs& a, int co_t) {
   return a.w2 == nullptr || (a.c2_0 / co_t == (a.c2_0 + a.cin2 - 1) / co_t);
 }
 
-// validate the descriptor and build the op for `hint` (d->tile_hint is ignored here)
-static int build_conv_op(const glsdet_conv_desc* d, int hint, OpRecord& op, const glsdet_conv_chain* chain = nullptr,
+// the three dtype instantiations of dispatch_tile, for any of the three argument blocks
+template <typename Args>
+static std::function<int(hipStream_t)> tile_launcher(const Args& m, int co_t, int px_t, int kb, int xdt, int ydt) {
+  return [m, co_t, px_t, kb, xdt, ydt](hipStream_t st) -> int {
+    return with_conv_types(xdt, ydt, [&](auto t, auto to) { return dispatch_tile<decltype(t), decltype(to)>(m, co_t, px_t, kb, st); });
+  };
+}
+
+// validate the descriptor and build the op for `hint_raw` (d->tile_hint is ignored here)
+static int build_conv_op(const glsdet_conv_desc* d, int hint_raw, OpRecord& op, const glsdet_conv_chain* chain = nullptr,
                          int gn_groups = 0, void* gn_stats = nullptr) {
+  const TileHint hint = decode_tile_hint(hint_raw);
+  if (!hint.valid) return refuse_unknown_hint(hint, gn_stats ? "conv2d_gnstats" : (chain ? "conv2d_chain" : "conv2d"));
   ConvArgs a;
   op.kind = 0;
   int rc = make_conv_args(d, hint, a, &op.flops, &op.bytes);
@@ -780,7 +771,7 @@ static int build_conv_op(const glsdet_conv_desc* d, int hint, OpRecord& op, cons
     a.gn_part = (double*)gn_stats;
     a.gn_groups = gn_groups;
     a.gn_cpg = d->y.c / gn_groups;
-    if (hint < 8 || hint > 11) GLS_FAIL(GLSDET_E_ARG, "conv2d_gnstats: tile_hint must name a halo ring kernel (8..11)");
+    if (!hint.ring() || hint.geo) GLS_FAIL(GLSDET_E_ARG, "conv2d_gnstats: tile_hint must name a halo ring kernel (8..11)");
     if (conv_halo_try(a, d->x.dtype, d->y.dtype, hint, &op) == 0) {
       op.name += " +gn stats";
       return 0;
@@ -789,47 +780,51 @@ static int build_conv_op(const glsdet_conv_desc* d, int hint, OpRecord& op, cons
   }
   const glsdet_view &x = d->x, &y = d->y;
   const int xdt = x.dtype, ydt = y.dtype;
-  // tile_hint: 0 auto, 1 generic kernel, 2 halo kernel, 4 halo kernel with wave-private weight staging,
-  // 5 halo kernel with 64-row cout tiles also for wide layers,
-  // 8 / 9 halo kernel with the weight tiles in an LDS-DMA ring (10 / 11: 64-byte channel chunks), 3 weight-stationary
-  // 1x1 kernel (6 / 7 were the persistent LDS-DMA halo kernel, removed in round 2: 1.3-1.9x slower),
-  // else co<<16|px (generic)
-  if (hint == 3) {
+  if (hint.family == TileHint::WS1X1) {
     if (!a.w2 && conv1x1_ws_try(a, xdt, ydt, &op) == 0) return 0;
     GLS_FAIL(GLSDET_E_ARG, "conv2d: the weight-stationary 1x1 kernel does not apply to this problem");
   }
-  if (hint == 6 || hint == 7) GLS_FAIL(GLSDET_E_ARG, "conv2d: tile_hint 6 / 7 (persistent LDS-DMA halo kernel) no longer exist");
-  if (hint >= 16 && hint < 64 && !a.w2) {   // persistent LDS-DMA GEMM kernel for 1x1 convs (conv_gemm.hip), variant hint - 16
+  if (hint.family == TileHint::GEMM && !a.w2) {   // persistent LDS-DMA GEMM kernel for 1x1 convs (conv_gemm.hip)
     if (conv_gemm_try(a, xdt, ydt, hint, &op) == 0) return 0;
-    GLS_FAIL(GLSDET_E_ARG, "conv2d: the persistent 1x1 kernel (variant %d) does not apply to this problem", hint - 16);
+    GLS_FAIL(GLSDET_E_ARG, "conv2d: the persistent 1x1 kernel (variant %d) does not apply to this problem", hint.variant);
   }
+  // (a GEMM hint on a chained conv has always run the generic kernel on the tile pick_tile chooses)
   if (conv_halo_try(a, xdt, ydt, hint, &op) == 0) return 0;
-  if (hint == 2 || hint == 4 || hint == 5 || (hint >= 8 && hint <= 13) || (hint >= 0x100 && hint < 0x300))
-    GLS_FAIL(GLSDET_E_ARG, "conv2d: the halo kernel does not apply to this problem");
+  if (hint.halo_family()) GLS_FAIL(GLSDET_E_ARG, "conv2d: the halo kernel does not apply to this problem");
 
   int co_t, px_t, kb;
-  pick_tile(a, dtype_size(x.dtype), hint >= 0x10000 ? hint : 0, &co_t, &px_t, &kb);
-  if (hint >= 0x10000 && co_t > 32 && a.cout_pad <= co_t / 2) GLS_FAIL(GLSDET_E_ARG, "conv2d: tile %dx%d is mostly padding here", co_t, px_t);
+  pick_tile(a, dtype_size(x.dtype), hint, &co_t, &px_t, &kb);
+  if (hint.explicit_tile() && co_t > 32 && a.cout_pad <= co_t / 2) GLS_FAIL(GLSDET_E_ARG, "conv2d: tile %dx%d is mostly padding here", co_t, px_t);
   if (co_t == 0 || (a.w2 && co_t == 32)) GLS_FAIL(GLSDET_E_ARG, "conv2d_chain: no tile of the generic kernel takes this chained problem");
   if (!chain_fits(a, co_t)) GLS_FAIL(GLSDET_E_ARG, "conv2d_chain: the chained input channels straddle two cout tiles of %d", co_t);
   // the chained form is compiled for K steps that stay inside one filter tap only (dispatch_tile: UT)
-  if (a.w2 && (((long)a.Cin * dtype_size(xdt)) % kb != 0 || getenv("GLSDET_NO_UT") != nullptr))
-    GLS_FAIL(GLSDET_E_ARG, "conv2d_chain: the generic kernel chains only when Cin is a whole number of K steps");
+  const bool ut = ((long)a.Cin * dtype_size(xdt)) % kb == 0 && getenv("GLSDET_NO_UT") == nullptr;
+  if (a.w2 && !ut) GLS_FAIL(GLSDET_E_ARG, "conv2d_chain: the generic kernel chains only when Cin is a whole number of K steps");
+  // ... and so is the eight-wave tile, which has no chained form either
+  if (px_t == 256 && (!ut || a.w2))
+    GLS_FAIL(GLSDET_E_ARG, "conv2d: the 128x256 tile needs Cin to be a whole number of K steps and no chained conv");
   char nm[112];
   snprintf(nm, sizeof nm, "conv_igemm<%s,%s,%dx%d,kb%d> %dx%d s%d cin%d cout%d%s", xdt ? "f32" : "f16",
            ydt ? "f32" : "f16", co_t, px_t, kb, d->R, d->S, d->stride, x.c, y.c, a.w2 ? " +1x1" : "");
   op.name = nm;
-  op.launch = [a, co_t, px_t, kb, xdt, ydt](hipStream_t st) -> int {
-    if (xdt == GLSDET_F16 && ydt == GLSDET_F16) return dispatch_tile<f16, f16>(a, co_t, px_t, kb, st);
-    if (xdt == GLSDET_F16 && ydt == GLSDET_F32) return dispatch_tile<f16, float>(a, co_t, px_t, kb, st);
-    return dispatch_tile<float, float>(a, co_t, px_t, kb, st);
-  };
+  op.launch = tile_launcher(a, co_t, px_t, kb, xdt, ydt);
   return 0;
 }
 
+// name and launcher of a grouped ("multi") / batched op on the generic kernel
+template <typename Args>
+static void name_group_op(OpRecord& op, const char* form, const Args& m, int n, int co_t, int px_t, int kb, const glsdet_conv_desc& d0) {
+  char nm[112];
+  snprintf(nm, sizeof nm, "conv_igemm_%s[%d]<%s,%s,%dx%d,kb%d> %dx%d s%d cin%d cout%d", form, n, d0.x.dtype ? "f32" : "f16",
+           d0.y.dtype ? "f32" : "f16", co_t, px_t, kb, d0.R, d0.S, d0.stride, d0.x.c, d0.y.c);
+  op.name = nm;
+  op.launch = tile_launcher(m, co_t, px_t, kb, d0.x.dtype, d0.y.dtype);
+}
+
 // The batched form: 9..GLS_BATCH problems whose argument blocks differ in the operand addresses only.
-static int build_conv_batch_op(const glsdet_conv_desc* d, int32_t n, int hint, OpRecord& op) {
-  if (hint && hint < 0x10000) GLS_FAIL(GLSDET_E_ARG, "conv2d_multi: more than %d descriptors run on the generic tiles only (hint %d)", GLS_MULTI, hint);
+static int build_conv_batch_op(const glsdet_conv_desc* d, int32_t n, const TileHint& hint, OpRecord& op) {
+  if (hint.family != TileHint::AUTO && !hint.explicit_tile())
+    GLS_FAIL(GLSDET_E_ARG, "conv2d_multi: more than %d descriptors run on the generic tiles only (hint %d)", GLS_MULTI, hint.raw);
   ConvArgsB m = {};
   m.n = n;
   op.kind = 0;
@@ -863,23 +858,16 @@ static int build_conv_batch_op(const glsdet_conv_desc* d, int32_t n, int hint, O
   ConvArgs probe = m.base;
   const long Mtot = (long)m.base.M * n;
   probe.M = (int)(Mtot > 0x7fffffffL ? 0x7fffffffL : Mtot);
-  pick_tile(probe, dtype_size(d[0].x.dtype), hint >= 0x10000 ? hint : 0, &co_t, &px_t, &kb);
+  pick_tile(probe, dtype_size(d[0].x.dtype), hint, &co_t, &px_t, &kb);
   if (co_t == 32) { co_t = 64; px_t = 64; }
   if (px_t == 256) { co_t = 128; px_t = 128; }
-  const int xdt = d[0].x.dtype, ydt = d[0].y.dtype;
-  char nm[112];
-  snprintf(nm, sizeof nm, "conv_igemm_batch[%d]<%s,%s,%dx%d,kb%d> %dx%d s%d cin%d cout%d", n, xdt ? "f32" : "f16",
-           ydt ? "f32" : "f16", co_t, px_t, kb, d[0].R, d[0].S, d[0].stride, d[0].x.c, d[0].y.c);
-  op.name = nm;
-  op.launch = [m, co_t, px_t, kb, xdt, ydt](hipStream_t st) -> int {
-    if (xdt == GLSDET_F16 && ydt == GLSDET_F16) return dispatch_tile_batch<f16, f16>(m, co_t, px_t, kb, st);
-    if (xdt == GLSDET_F16 && ydt == GLSDET_F32) return dispatch_tile_batch<f16, float>(m, co_t, px_t, kb, st);
-    return dispatch_tile_batch<float, float>(m, co_t, px_t, kb, st);
-  };
+  name_group_op(op, "batch", m, n, co_t, px_t, kb, d[0]);
   return 0;
 }
 
-static int build_conv_multi_op(const glsdet_conv_desc* d, int32_t n, int hint, OpRecord& op) {
+static int build_conv_multi_op(const glsdet_conv_desc* d, int32_t n, int hint_raw, OpRecord& op) {
+  const TileHint hint = decode_tile_hint(hint_raw);
+  if (!hint.valid) return refuse_unknown_hint(hint, "conv2d_multi");
   if (d && n > GLS_MULTI && n <= GLS_BATCH) return build_conv_batch_op(d, n, hint, op);
   if (!d || n < 1 || n > GLS_MULTI) GLS_FAIL(GLSDET_E_ARG, "conv2d_multi: 1..%d descriptors (up to %d of one geometry)", GLS_MULTI, GLS_BATCH);
   ConvArgsN m = {};
@@ -899,26 +887,18 @@ static int build_conv_multi_op(const glsdet_conv_desc* d, int32_t n, int hint, O
         a.pad != b.pad || a.Cin != b.Cin || a.Cout != b.Cout)
       GLS_FAIL(GLSDET_E_ARG, "conv2d_multi: descriptor %d is not of the shape class of descriptor 0", i);
   }
-  if ((hint >= 8 && hint <= 11) || (hint >= 0x100 && hint < 0x300)) {          // the grouped ring kernel (conv_halo.hip; bits 8..9: tile geometry); no silent fall-back: the tuner asks per hint
+  if (hint.ring() || hint.geo) {          // the grouped ring kernel (conv_halo.hip); no silent fall-back: the tuner asks per hint
     if (conv_halo_multi_try(m, d[0].x.dtype, d[0].y.dtype, hint, &op))
-      GLS_FAIL(GLSDET_E_ARG, "conv2d_multi: the grouped halo kernel (hint %d) does not apply to this shape class", hint);
+      GLS_FAIL(GLSDET_E_ARG, "conv2d_multi: the grouped halo kernel (hint %d) does not apply to this shape class", hint.raw);
     return 0;
   }
   int co_t, px_t, kb;
   ConvArgs probe = m.p[0];
   probe.M = (int)(Mtot > 0x7fffffffL ? 0x7fffffffL : Mtot);
-  pick_tile(probe, dtype_size(d[0].x.dtype), hint >= 0x10000 ? hint : 0, &co_t, &px_t, &kb);
+  pick_tile(probe, dtype_size(d[0].x.dtype), hint, &co_t, &px_t, &kb);      // (every other family: the tile chosen there)
   if (co_t == 32) { co_t = 64; px_t = 64; }
-  const int xdt = d[0].x.dtype, ydt = d[0].y.dtype;
-  char nm[112];
-  snprintf(nm, sizeof nm, "conv_igemm_multi[%d]<%s,%s,%dx%d,kb%d> %dx%d s%d cin%d cout%d", n, xdt ? "f32" : "f16",
-           ydt ? "f32" : "f16", co_t, px_t, kb, d[0].R, d[0].S, d[0].stride, d[0].x.c, d[0].y.c);
-  op.name = nm;
-  op.launch = [m, co_t, px_t, kb, xdt, ydt](hipStream_t st) -> int {
-    if (xdt == GLSDET_F16 && ydt == GLSDET_F16) return dispatch_tile_multi<f16, f16>(m, co_t, px_t, kb, st);
-    if (xdt == GLSDET_F16 && ydt == GLSDET_F32) return dispatch_tile_multi<f16, float>(m, co_t, px_t, kb, st);
-    return dispatch_tile_multi<float, float>(m, co_t, px_t, kb, st);
-  };
+  if (!tile_compiled<false>(co_t, px_t)) GLS_FAIL(GLSDET_E_ARG, "conv2d_multi: no kernel for tile %dx%d", co_t, px_t);
+  name_group_op(op, "multi", m, n, co_t, px_t, kb, d[0]);
   return 0;
 }
 
@@ -942,22 +922,22 @@ static int time_variants(std::vector<OpRecord>& ops, const std::vector<int>& ids
   GLS_HIP(hipEventCreate(&e1));
   std::vector<float> us(ops.size(), 1e30f);
   std::vector<char> dead(ops.size(), 0);
+  auto measure = [&](size_t i, int reps) {           // `reps` back-to-back launches; a candidate keeps its fastest round, a failure retires it
+    if (dead[i]) return;
+    int rc = 0;
+    (void)hipEventRecord(e0, st);
+    for (int r = 0; r < reps && !rc; ++r) rc = ops[i].launch(st);
+    (void)hipEventRecord(e1, st);
+    if (hipEventSynchronize(e1) != hipSuccess || rc) { dead[i] = 1; return; }
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    const float u = ms * 1000.f / reps;
+    if (u < us[i]) us[i] = u;
+  };
   for (size_t i = 0; i < ops.size(); ++i)
     if (ops[i].launch(st)) dead[i] = 1;
-  for (int t = 0; t < TRIALS; ++t) {
-    for (size_t i = 0; i < ops.size(); ++i) {
-      if (dead[i]) continue;
-      int rc = 0;
-      (void)hipEventRecord(e0, st);
-      for (int r = 0; r < REPS && !rc; ++r) rc = ops[i].launch(st);
-      (void)hipEventRecord(e1, st);
-      if (hipEventSynchronize(e1) != hipSuccess || rc) { dead[i] = 1; continue; }
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, e0, e1);
-      const float u = ms * 1000.f / REPS;
-      if (u < us[i]) us[i] = u;
-    }
-  }
+  for (int t = 0; t < TRIALS; ++t)
+    for (size_t i = 0; i < ops.size(); ++i) measure(i, REPS);
   // play-off: candidates within 4 % of the fastest are measured again, longer (near-ties used to flip between runs and
   // moved a whole workload by up to 1.5 %: the same build picked ring vs ring_k64 for the tower convs on two boxes)
   float lo = 1e30f;
@@ -970,18 +950,7 @@ static int time_variants(std::vector<OpRecord>& ops, const std::vector<int>& ids
     constexpr int REPS2 = 12;
     for (size_t i : close) us[i] = 1e30f;
     for (int t = 0; t < 4; ++t)
-      for (size_t i : close) {
-        if (dead[i]) continue;
-        int rc = 0;
-        (void)hipEventRecord(e0, st);
-        for (int r = 0; r < REPS2 && !rc; ++r) rc = ops[i].launch(st);
-        (void)hipEventRecord(e1, st);
-        if (hipEventSynchronize(e1) != hipSuccess || rc) { dead[i] = 1; continue; }
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        const float u = ms * 1000.f / REPS2;
-        if (u < us[i]) us[i] = u;
-      }
+      for (size_t i : close) measure(i, REPS2);
   }
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
@@ -994,46 +963,63 @@ static int time_variants(std::vector<OpRecord>& ops, const std::vector<int>& ids
   return 0;
 }
 
-extern "C" int glsdet_conv2d_multi_tune(const glsdet_conv_desc* d, int32_t n, void* stream, int32_t* best_hint,
-                                        float* best_us) {
-  if (!d || !best_hint) GLS_FAIL(GLSDET_E_ARG, "conv2d_multi_tune: null argument");
-  hipStream_t st = (hipStream_t)stream;
-  const int hints[] = {(128 << 16) | 128, (64 << 16) | 128, (64 << 16) | 64, (64 << 16) | 64 | 0x8000,
-                       (64 << 16) | 128 | 0x8000, (128 << 16) | 128 | 0x8000, 8, 9, 10, 11};
-  std::vector<OpRecord> ops;
-  std::vector<int> ids;
-  const bool no_ring = getenv("GLSDET_NO_RING_MULTI") != nullptr;       // A/B switch for measurements
-  std::vector<int> cand(hints, hints + sizeof(hints) / sizeof(hints[0]));
-  if (!getenv("GLSDET_NO_TILE_GEO") && (d[0].stride == 1 || d[0].stride == 2) && d[0].R == 3 && !no_ring) {
-    for (int geo = 1; geo <= 2; ++geo) {             // tile geometries with >= 3 % fewer tiles over the whole group
-      int th, tw;
-      tile_geo_dims(geo, &th, &tw);
-      long t0 = 0, t1 = 0;
-      for (int i = 0; i < n; ++i) {
-        t0 += (long)((d[i].y.h + 7) / 8) * ((d[i].y.w + 15) / 16);
-        t1 += (long)((d[i].y.h + th - 1) / th) * ((d[i].y.w + tw - 1) / tw);
-      }
-      if (t1 * 100 <= t0 * 97)
-        for (int h : {8, 9, 10, 11})
-          if (d[0].stride == 1 || h >= 10) cand.push_back((geo << 8) | h);
-    }
-  }
-  for (int h : cand) {
-    OpRecord op;
-    if (no_ring && (h & 0xff) >= 8 && (h & 0xff) <= 11 && h < 0x10000) continue;
-    if (build_conv_multi_op(d, n, h, op)) continue;
-    ops.push_back(std::move(op));
-    ids.push_back(h);
-  }
+// the tail of every *_tune entry point: time the candidates, report the fastest id
+static int tune_report(std::vector<OpRecord>& ops, const std::vector<int>& ids, void* stream, const char* none_applies,
+                       int32_t* best_hint, float* best_us) {
   float best = 1e30f;
   int bh = 0, any = 0;
-  int rc = time_variants(ops, ids, st, &bh, &best, &any);
+  int rc = time_variants(ops, ids, (hipStream_t)stream, &bh, &best, &any);
   if (rc) return rc;
-  if (!any) GLS_FAIL(GLSDET_E_ARG, "conv2d_multi_tune: no variant applies");
+  if (!any) GLS_FAIL(GLSDET_E_ARG, "%s", none_applies);
   *best_hint = bh;
   if (best_us) *best_us = best;
   set_error("");
   return 0;
+}
+
+// Other tile geometries of the ring kernels (conv_common.h TileGeo) are offered where they need >= 3 % fewer tiles over
+// all n problems (output extents ho[i] x wo[i]): appends the ring hints of those geometries (stride 2: the 64-byte-chunk
+// forms only) and, with ring8, the 8-wave form's.
+static void add_geometry_hints(std::vector<int>& cand, const int* ho, const int* wo, int n, int stride, bool ring8) {
+  auto tiles = [&](int th, int tw) {
+    long t = 0;
+    for (int i = 0; i < n; ++i) t += (long)((ho[i] + th - 1) / th) * ((wo[i] + tw - 1) / tw);
+    return t;
+  };
+  for (int geo = 1; geo <= 2; ++geo) {
+    int th, tw;
+    tile_geo_dims(geo, &th, &tw);
+    if (tiles(th, tw) * 100 <= tiles(8, 16) * 97)
+      for (const bool k64 : {false, true})
+        for (const int co : {64, 128})
+          if (stride == 1 || k64) cand.push_back(encode_ring_hint(geo, co, k64));
+    tile_geo8_dims(geo, &th, &tw);
+    if (ring8 && stride == 1 && tiles(th, tw) * 100 <= tiles(8, 32) * 97) cand.push_back(encode_ring8_hint(geo, true));
+  }
+}
+
+extern "C" int glsdet_conv2d_multi_tune(const glsdet_conv_desc* d, int32_t n, void* stream, int32_t* best_hint,
+                                        float* best_us) {
+  if (!d || !best_hint) GLS_FAIL(GLSDET_E_ARG, "conv2d_multi_tune: null argument");
+  std::vector<int> cand = {(128 << 16) | 128, (64 << 16) | 128, (64 << 16) | 64, (64 << 16) | 64 | 0x8000,
+                           (64 << 16) | 128 | 0x8000, (128 << 16) | 128 | 0x8000, 8, 9, 10, 11};
+  std::vector<OpRecord> ops;
+  std::vector<int> ids;
+  const bool no_ring = getenv("GLSDET_NO_RING_MULTI") != nullptr;       // A/B switch for measurements
+  if (!getenv("GLSDET_NO_TILE_GEO") && (d[0].stride == 1 || d[0].stride == 2) && d[0].R == 3 && !no_ring) {
+    int ho[GLS_BATCH], wo[GLS_BATCH];
+    const int ng = n < GLS_BATCH ? n : GLS_BATCH;
+    for (int i = 0; i < ng; ++i) { ho[i] = d[i].y.h; wo[i] = d[i].y.w; }
+    add_geometry_hints(cand, ho, wo, ng, d[0].stride, false);
+  }
+  for (int h : cand) {
+    OpRecord op;
+    if (no_ring && decode_tile_hint(h).ring()) continue;
+    if (build_conv_multi_op(d, n, h, op)) continue;
+    ops.push_back(std::move(op));
+    ids.push_back(h);
+  }
+  return tune_report(ops, ids, stream, "conv2d_multi_tune: no variant applies", best_hint, best_us);
 }
 
 extern "C" int glsdet_conv2d(const glsdet_conv_desc* d, void* stream) {
@@ -1058,8 +1044,8 @@ static int build_bneck_op(const glsdet_conv_desc* c1, const glsdet_conv_desc* c2
   ConvArgs a1;
   double f1, b1, f2, b2;
   int rc;
-  if ((rc = make_conv_args(c1, 0, a1, &f1, &b1))) return rc;
-  if ((rc = make_conv_args(c2, 0, b.c, &f2, &b2))) return rc;
+  if ((rc = make_conv_args(c1, decode_tile_hint(0), a1, &f1, &b1))) return rc;
+  if ((rc = make_conv_args(c2, decode_tile_hint(0), b.c, &f2, &b2))) return rc;
   const glsdet_view &m1 = c1->y, &m2 = c2->x;
   if (c1->R != 1 || c1->S != 1 || c1->stride != 1 || c1->pad != 0 || c1->res.base || (c1->act & GLSDET_ACT_RES_FIRST))
     GLS_FAIL(GLSDET_E_ARG, "bottleneck: the first conv must be a plain 1x1 (stride 1, no padding, no residual)");
@@ -1108,15 +1094,7 @@ extern "C" int glsdet_bottleneck_tune(const glsdet_conv_desc* c1, const glsdet_c
     ops.push_back(std::move(op));
     ids.push_back(h);
   }
-  float best = 1e30f;
-  int bh = 0, any = 0;
-  int rc = time_variants(ops, ids, (hipStream_t)stream, &bh, &best, &any);
-  if (rc) return rc;
-  if (!any) GLS_FAIL(GLSDET_E_ARG, "bottleneck_tune: the fused kernel does not apply");
-  *best_hint = bh;
-  if (best_us) *best_us = best;
-  set_error("");
-  return 0;
+  return tune_report(ops, ids, stream, "bottleneck_tune: the fused kernel does not apply", best_hint, best_us);
 }
 
 // conv + GroupNorm partials of its output (the tower convs of gfl_head.py:128-152: conv -> GN -> ReLU): the statistics
@@ -1143,15 +1121,7 @@ extern "C" int glsdet_conv2d_gnstats_tune(const glsdet_conv_desc* d, int32_t gro
     ops.push_back(std::move(op));
     ids.push_back(h);
   }
-  float best = 1e30f;
-  int bh = 0, any = 0;
-  int rc = time_variants(ops, ids, (hipStream_t)stream, &bh, &best, &any);
-  if (rc) return rc;
-  if (!any) GLS_FAIL(GLSDET_E_ARG, "conv2d_gnstats_tune: no halo ring kernel applies");
-  *best_hint = bh;
-  if (best_us) *best_us = best;
-  set_error("");
-  return 0;
+  return tune_report(ops, ids, stream, "conv2d_gnstats_tune: no halo ring kernel applies", best_hint, best_us);
 }
 
 // Measure every kernel/tile variant that applies to this exact problem on the device (its
@@ -1169,43 +1139,22 @@ extern "C" int glsdet_conv2d_chain_tune(const glsdet_conv_desc* d, const glsdet_
 }
 static int conv_tune(const glsdet_conv_desc* d, const glsdet_conv_chain* c, void* stream, int32_t* best_hint, float* best_us) {
   if (!d || !best_hint) GLS_FAIL(GLSDET_E_ARG, "conv2d_tune: null argument");
-  hipStream_t st = (hipStream_t)stream;
   // (6 / 7, the persistent LDS-DMA halo kernel, is not offered: slower than 8 / 9 on every layer measured)
-  const int hints[] = {2, 4, 5, 8, 9, 10, 11, 12, 13, 3, 16, 20, 22, 24, 25, 29, (128 << 16) | 128, (64 << 16) | 128, (64 << 16) | 64, (32 << 16) | 128,
-                       (64 << 16) | 64 | 0x8000, (64 << 16) | 128 | 0x8000, (128 << 16) | 128 | 0x8000, (128 << 16),
-                       (128 << 16) | 0x8000};
+  std::vector<int> cand = {2, 4, 5, 8, 9, 10, 11, 12, 13, 3, 16, 20, 22, 24, 25, 29, (128 << 16) | 128, (64 << 16) | 128, (64 << 16) | 64,
+                           (32 << 16) | 128, (64 << 16) | 64 | 0x8000, (64 << 16) | 128 | 0x8000, (128 << 16) | 128 | 0x8000, (128 << 16),
+                           (128 << 16) | 0x8000};
   std::vector<OpRecord> ops;
   std::vector<int> ids;
-  std::vector<int> cand(hints, hints + sizeof(hints) / sizeof(hints[0]));
-  if (!c && (d->stride == 1 || (d->stride == 2 && d->R == 3)) && d->R == d->S && d->R >= 3 && !getenv("GLSDET_NO_TILE_GEO")) {
-    // other tile geometries of the ring kernels (conv_common.h TileGeo): offered where they need >= 3 % fewer tiles
-    const int Ho = d->y.h, Wo = d->y.w;
-    auto tiles = [&](int th, int tw) { return (long)((Ho + th - 1) / th) * ((Wo + tw - 1) / tw); };
-    for (int geo = 1; geo <= 2; ++geo) {
-      int th, tw;
-      tile_geo_dims(geo, &th, &tw);
-      if (tiles(th, tw) * 100 <= tiles(8, 16) * 97)
-        for (int h : {8, 9, 10, 11})
-          if (d->stride == 1 || h >= 10) cand.push_back((geo << 8) | h);
-      tile_geo8_dims(geo, &th, &tw);
-      if (d->stride == 1 && tiles(th, tw) * 100 <= tiles(8, 32) * 97) cand.push_back((geo << 8) | 13);
-    }
-  }
+  if (!c && (d->stride == 1 || (d->stride == 2 && d->R == 3)) && d->R == d->S && d->R >= 3 && !getenv("GLSDET_NO_TILE_GEO"))
+    add_geometry_hints(cand, &d->y.h, &d->y.w, 1, d->stride, true);
   for (int h : cand) {
     OpRecord op;
-    if (h >= 0x10000 && (h >> 16) == 128 && (h & 0xff) == 0 && (c || d->y.c <= 64)) continue;      // the eight-wave tile: wide layers, no chain
+    const TileHint th = decode_tile_hint(h);
+    if (th.px_t == 256 && (c || d->y.c <= 64)) continue;      // the eight-wave tile: wide layers, no chain
     if (build_conv_op(d, h, op, c)) continue;          // variant does not apply
-    if (h >= 0x10000 && (h >> 16) == 32 && d->y.c > 32) continue;
+    if (th.co_t == 32 && d->y.c > 32) continue;
     ops.push_back(std::move(op));
     ids.push_back(h);
   }
-  float best = 1e30f;
-  int bh = 0, any = 0;
-  int rc = time_variants(ops, ids, st, &bh, &best, &any);
-  if (rc) return rc;
-  if (!any) GLS_FAIL(GLSDET_E_ARG, "conv2d_tune: no variant applies");
-  *best_hint = bh;
-  if (best_us) *best_us = best;
-  set_error("");
-  return 0;
+  return tune_report(ops, ids, stream, "conv2d_tune: no variant applies", best_hint, best_us);
 }

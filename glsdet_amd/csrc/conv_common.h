@@ -1,6 +1,8 @@
 // Shared by the convolution kernels (conv.hip: generic implicit GEMM; conv_halo.hip:
 // stride-1 kxk with the input patch staged once per channel chunk).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace glsdet {
@@ -695,13 +697,105 @@ struct HaloArgsN {
   int tx[GLS_MULTI], ty[GLS_MULTI];      // 8 x 16 tiles per row / column of each problem
   int n;
 };
-int conv_halo_try(const ConvArgs& a, int xdt, int ydt, int hint, OpRecord* op);
-int conv_halo_multi_try(const ConvArgsN& m, int xdt, int ydt, int hint, OpRecord* op);
+
+// ---- tile_hint, decoded ONCE (the encoding: include/glsdet_hip.h, at glsdet_conv_desc.tile_hint) -----------------------
+struct TileHint {
+  enum Family { AUTO, GENERIC, HALO, HALO_WPRIV, HALO_64, RING, RING8, WS1X1, GEMM };
+  int raw;                  // the encoded value (error texts)
+  Family family;
+  bool valid;               // false: a value the header does not document (6 / 7: retired)
+  int co_pref;              // RING: 64- / 128-row cout tiles (8, 10 / 9, 11)
+  bool k64;                 // RING / RING8: 64-byte channel chunks (10, 11 / 13); GENERIC tile: 64-byte K steps (bit 15)
+  int geo;                  // RING / RING8: pixel-tile geometry 0 / 1 / 2 (bits 8..9)
+  int co_t, px_t;           // GENERIC: the explicit tile co << 16 | px (px 0 = 256); 0 x 0 = chosen by pick_tile (hint 1)
+  int dbg;                  // GENERIC tile: diagnostic switches (bits 8..10)
+  int variant;              // GEMM: index into the variant table of conv_gemm.hip (hint - 16)
+  bool ring() const { return family == RING; }
+  bool halo_family() const { return family == HALO || family == HALO_WPRIV || family == HALO_64 || family == RING || family == RING8; }
+  bool explicit_tile() const { return family == GENERIC && co_t != 0; }
+};
+inline TileHint decode_tile_hint(int h) {
+  TileHint t = {};
+  t.raw = h;
+  t.family = TileHint::AUTO;
+  t.valid = true;
+  if (h >= 0x10000) {
+    t.family = TileHint::GENERIC;
+    t.co_t = h >> 16;
+    t.px_t = (h & 0xff) ? (h & 0xff) : 256;
+    t.k64 = (h & 0x8000) != 0;
+    t.dbg = (h >> 8) & 7;
+    const int co = t.co_t, px = t.px_t;          // the tiles any form of the generic kernel is compiled for (conv.hip: with_tile)
+    t.valid = !(h & 0x7800) && ((px == 128 && (co == 128 || co == 64 || co == 32)) || (co == 64 && px == 64) || (co == 128 && px == 256));
+    return t;
+  }
+  t.geo = (h >= 0x100 && h < 0x300) ? (h >> 8) : 0;
+  const int base = t.geo ? (h & 0xff) : h;
+  static const TileHint::Family small[6] = {TileHint::AUTO, TileHint::GENERIC, TileHint::HALO, TileHint::WS1X1, TileHint::HALO_WPRIV, TileHint::HALO_64};
+  if (base >= 0 && base <= 5) {
+    t.family = small[base];
+  } else if (base >= 8 && base <= 11) {
+    t.family = TileHint::RING;
+    t.co_pref = (base & 1) ? 128 : 64;
+    t.k64 = base >= 10;
+  } else if (base == 12 || base == 13) {
+    t.family = TileHint::RING8;
+    t.k64 = base == 13;
+  } else if (base >= 16 && base < 32) {
+    t.family = TileHint::GEMM;
+    t.variant = base - 16;
+  } else {
+    t.valid = false;
+  }
+  // geometry bits: ring hints only (the 8-wave form: its 64-byte-chunk kernel only)
+  if (t.geo && !(t.family == TileHint::RING || (t.family == TileHint::RING8 && t.k64))) t.valid = false;
+  return t;
+}
+// the ring hint of a geometry / cout tile / chunk size (the tuners' candidate lists)
+inline int encode_ring_hint(int geo, int co_pref, bool k64) { return (geo << 8) | (8 + (co_pref == 128 ? 1 : 0) + (k64 ? 2 : 0)); }
+inline int encode_ring8_hint(int geo, bool k64) { return (geo << 8) | (k64 ? 13 : 12); }
+// every entry point refuses what decode_tile_hint does not know, when the op is built
+inline int refuse_unknown_hint(const TileHint& t, const char* who) {
+  if (t.raw == 6 || t.raw == 7) GLS_FAIL(GLSDET_E_ARG, "%s: tile_hint 6 / 7 (persistent LDS-DMA halo kernel) no longer exist", who);
+  GLS_FAIL(GLSDET_E_ARG, "%s: tile_hint %d (0x%x) is not a documented value (include/glsdet_hip.h)", who, t.raw, t.raw);
+}
+
+// runtime value -> template argument: the host dispatchers call generic lambdas with these
+template <int N> using IC = std::integral_constant<int, N>;
+// the (x, y) dtype pairs the conv kernels are compiled for: f(T{}, TO{})
+template <typename F>
+inline int with_conv_types(int xdt, int ydt, F&& f) {
+  if (xdt == GLSDET_F16 && ydt == GLSDET_F16) return f(f16{}, f16{});
+  if (xdt == GLSDET_F16 && ydt == GLSDET_F32) return f(f16{}, float{});
+  return f(float{}, float{});
+}
+// cout tiles of CO_T rows and flat pixel tiles of PX_T of one problem (generic kernel, conv_gemm.hip)
+template <int CO_T, int PX_T>
+inline void fill_flat_tiles(ConvArgs& b) {
+  b.n_co_tiles = (b.cout_pad + CO_T - 1) / CO_T;
+  // tiles that would only cover the zero padding of cout_pad are never created
+  if ((b.n_co_tiles - 1) * CO_T >= b.Cout) b.n_co_tiles = (b.Cout + CO_T - 1) / CO_T;
+  gls_fastdiv(b.n_co_tiles, &b.nco_mul, &b.nco_sh);
+  b.n_px_tiles = (b.M + PX_T - 1) / PX_T;
+}
+// cout tiles of CO_T rows and TH x TW pixel tiles of one problem (halo kernels)
+template <int CO_T, int TH, int TW>
+inline void fill_halo_tiles(ConvArgs& b, int* tiles_x, int* tiles_y) {
+  b.n_co_tiles = (b.Cout + CO_T - 1) / CO_T;
+  *tiles_x = (b.Wo + TW - 1) / TW;
+  *tiles_y = (b.Ho + TH - 1) / TH;
+  gls_fastdiv(b.n_co_tiles, &b.nco_mul, &b.nco_sh);
+  gls_fastdiv(*tiles_x, &b.tx_mul, &b.tx_sh);
+  gls_fastdiv(*tiles_y, &b.ty_mul, &b.ty_sh);
+}
+
+int conv_halo_try(const ConvArgs& a, int xdt, int ydt, const TileHint& hint, OpRecord* op);
+int conv_halo_multi_try(const ConvArgsN& m, int xdt, int ydt, const TileHint& hint, OpRecord* op);
 // fused Bottleneck front (conv_bneck.hip); hint 0 / 1 = 128- / 64-byte channel chunks; returns 1 if it does not apply
 int conv_bneck_try(const BneckArgs& b, int dt, int hint, OpRecord* op);
 // weight-stationary persistent 1x1 kernel (conv1x1.hip), tile_hint 3; returns 1 if it does not apply
 int conv1x1_ws_try(const ConvArgs& a, int xdt, int ydt, OpRecord* op);
 // persistent LDS-DMA GEMM kernel for 1x1 convs (conv_gemm.hip), tile_hint 16 + variant; returns 1 if it does not apply
-int conv_gemm_try(const ConvArgs& a, int xdt, int ydt, int hint, OpRecord* op);
+int conv_gemm_try(const ConvArgs& a, int xdt, int ydt, const TileHint& hint, OpRecord* op);
 
 }  // namespace glsdet

@@ -352,6 +352,13 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvArgs a, const 
   gemm_wait_vm<0>();                               // the zero fills issued beyond the last stage land before the LDS is released
 }
 
+// residual / output offsets are 32-bit byte offsets from the view's base: does a view of the output extent fit?
+template <typename TO>
+static bool span_fits_32bit(const ConvArgs& a, long sn, long sh, long sw) {
+  const long span = ((long)(a.N - 1) * sn + (long)(a.Ho - 1) * sh + (long)(a.Wo - 1) * sw + a.Cout) * (long)sizeof(TO);
+  return span < 0x7fffffffL && sn >= 0 && sh >= 0 && sw >= 0;
+}
+
 template <typename T, typename TO, int CO_T, int PX_T, int NS, int KB, bool WRES>
 static int launch_gemm(const ConvArgs& a, hipStream_t st, bool dry) {
   constexpr int ES = (int)sizeof(T);
@@ -364,18 +371,8 @@ static int launch_gemm(const ConvArgs& a, hipStream_t st, bool dry) {
   const int lds = NS * STAGE + (WRES ? gm.np * CO_T * KB : 0) + CO_T * 8 + (a.res ? gemm_res_bytes<TO>(CO_T, PX_T) : 0);
   if (lds > 160 * 1024) return 1;
   ConvArgs b = a;
-  b.n_co_tiles = (a.cout_pad + CO_T - 1) / CO_T;
-  if ((b.n_co_tiles - 1) * CO_T >= a.Cout) b.n_co_tiles = (a.Cout + CO_T - 1) / CO_T;
-  gls_fastdiv(b.n_co_tiles, &b.nco_mul, &b.nco_sh);
-  // residual offsets are 32-bit byte offsets from the view's base
-  if (a.res) {
-    const long span = ((long)(a.N - 1) * a.r_sn + (long)(a.Ho - 1) * a.r_sh + (long)(a.Wo - 1) * a.r_sw + a.Cout) * (long)sizeof(TO);
-    if (span >= 0x7fffffffL || a.r_sn < 0 || a.r_sh < 0 || a.r_sw < 0) return 1;
-  }
-  {
-    const long span = ((long)(a.N - 1) * a.y_sn + (long)(a.Ho - 1) * a.y_sh + (long)(a.Wo - 1) * a.y_sw + a.Cout) * (long)sizeof(TO);
-    if (span >= 0x7fffffffL || a.y_sn < 0 || a.y_sh < 0 || a.y_sw < 0) return 1;
-  }
+  fill_flat_tiles<CO_T, PX_T>(b);
+  if ((a.res && !span_fits_32bit<TO>(a, a.r_sn, a.r_sh, a.r_sw)) || !span_fits_32bit<TO>(a, a.y_sn, a.y_sh, a.y_sw)) return 1;
   if (dry) return 0;
   int per_cu = (160 * 1024) / (lds + 512);
   if (per_cu > 6) per_cu = 6;
@@ -597,17 +594,12 @@ static int launch_gemm1(const ConvArgs& a, hipStream_t st, bool dry) {
   const int np = (kbytes + 127) / 128;
   if (np > 4) return 1;                                                    // K <= 512 bytes: everything at once
   const int lds = np * (CO_T + PX_T) * 128 + (a.res ? gemm_res_bytes<TO>(CO_T, PX_T) : 0);
-  if (a.res) {
-    const long span = ((long)(a.N - 1) * a.r_sn + (long)(a.Ho - 1) * a.r_sh + (long)(a.Wo - 1) * a.r_sw + a.Cout) * (long)sizeof(TO);
-    if (span >= 0x7fffffffL || a.r_sn < 0 || a.r_sh < 0 || a.r_sw < 0) return 1;
-  }
+  if (a.res && !span_fits_32bit<TO>(a, a.r_sn, a.r_sh, a.r_sw)) return 1;
   if (dry) return 0;
   ConvArgs b = a;
   if (const char* e = getenv("GLSDET_GEMM_DBG")) b.dbg = atoi(e);          // timing knock-outs (results are then invalid)
-  b.n_co_tiles = (a.cout_pad + CO_T - 1) / CO_T;
-  if ((b.n_co_tiles - 1) * CO_T >= a.Cout) b.n_co_tiles = (a.Cout + CO_T - 1) / CO_T;
-  gls_fastdiv(b.n_co_tiles, &b.nco_mul, &b.nco_sh);
-  const long grid = (long)b.n_co_tiles * ((a.M + PX_T - 1) / PX_T);
+  fill_flat_tiles<CO_T, PX_T>(b);
+  const long grid = (long)b.n_co_tiles * b.n_px_tiles;
   if (grid <= 0 || grid > 0x7fffffffL) return 1;
   auto kern = conv_gemm1_kernel<T, TO, CO_T, PX_T>;
   static int attr_lds = 64 * 1024;
@@ -665,18 +657,17 @@ static int gemm_dispatch(const ConvArgs& a, int v, hipStream_t st, bool dry) {
   return 1;
 }
 
-// tile_hint 16 .. 16 + N_GEMM_VARIANTS - 1.  Returns 1 when the variant does not apply to the problem.
-int conv_gemm_try(const ConvArgs& a, int xdt, int ydt, int hint, OpRecord* op) {
-  const int v = hint - 16;
-  if (v < 0 || v >= N_GEMM_VARIANTS) return 1;
+static_assert(N_GEMM_VARIANTS == 16, "decode_tile_hint (conv_common.h) knows tile_hint 16 .. 31");
+// TileHint::GEMM, variant 0 .. N_GEMM_VARIANTS - 1.  Returns 1 when the variant does not apply to the problem.
+int conv_gemm_try(const ConvArgs& a, int xdt, int ydt, const TileHint& hint, OpRecord* op) {
+  const int v = hint.variant;
+  if (hint.family != TileHint::GEMM || v >= N_GEMM_VARIANTS) return 1;
   if (a.R != 1 || a.S != 1 || a.stride != 1 || a.pad != 0 || a.w2 || a.gn_part) return 1;
   const GemmVariant& gv = GEMM_VARIANTS[v];
   if (gv.co_t > 32 && a.cout_pad <= gv.co_t / 2) return 1;                 // mostly padding
   if (gv.co_t == 32 && a.cout_pad > 32) return 1;
   auto run = [a, v, xdt, ydt](hipStream_t st, bool dry) -> int {
-    if (xdt == GLSDET_F16 && ydt == GLSDET_F16) return gemm_dispatch<f16, f16>(a, v, st, dry);
-    if (xdt == GLSDET_F16 && ydt == GLSDET_F32) return gemm_dispatch<f16, float>(a, v, st, dry);
-    return gemm_dispatch<float, float>(a, v, st, dry);
+    return with_conv_types(xdt, ydt, [&](auto t, auto to) { return gemm_dispatch<decltype(t), decltype(to)>(a, v, st, dry); });
   };
   if (run(nullptr, true)) return 1;
   char nm[112];

@@ -848,11 +848,8 @@ static int launch_halo_ring8(const ConvArgs& a, hipStream_t st) {
     attr_set = true;
   }
   ConvArgs b = a;
-  b.n_co_tiles = (a.Cout + 127) / 128;
-  const int tiles_x = (a.Wo + TW - 1) / TW, tiles_y = (a.Ho + TH - 1) / TH;
-  gls_fastdiv(b.n_co_tiles, &b.nco_mul, &b.nco_sh);
-  gls_fastdiv(tiles_x, &b.tx_mul, &b.tx_sh);
-  gls_fastdiv(tiles_y, &b.ty_mul, &b.ty_sh);
+  int tiles_x, tiles_y;
+  fill_halo_tiles<128, TH, TW>(b, &tiles_x, &tiles_y);
   const long grid = (long)b.n_co_tiles * tiles_x * tiles_y * a.N;
   if (grid <= 0 || grid > 0x7fffffffL) GLS_FAIL(GLSDET_E_ARG, "conv2d(halo ring8): grid %ld out of range", grid);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, st, b, tiles_x, tiles_y);
@@ -872,25 +869,32 @@ static int ring8_any(const ConvArgs& a, hipStream_t st) {
   return launch_halo_ring8<T, KS, RING, KB, GEO8, false>(a, st);
 }
 
-template <typename T>
-static int halo_ring8_dispatch(const ConvArgs& a, bool k64, int geo, hipStream_t st) {
-  if (geo == 0) {
-    switch (a.R) {
-      case 3: return k64 ? ring8_any<T, 3, 4, 64>(a, st) : ring8_any<T, 3, 3, 128>(a, st);
-      case 5: return k64 ? ring8_any<T, 5, 4, 64>(a, st) : ring8_any<T, 5, 3, 128>(a, st);
-      case 7: return k64 ? ring8_any<T, 7, 4, 64>(a, st) : ring8_any<T, 7, 3, 128>(a, st);
-    }
-  } else if (k64) {                // the other tile geometries: 64-byte channel chunks only (the form the tuner picks at 100 x 168)
-    switch (a.R * 4 + geo) {
-      case 3 * 4 + 1: return ring8_any<T, 3, 4, 64, 1>(a, st);
-      case 3 * 4 + 2: return ring8_any<T, 3, 4, 64, 2>(a, st);
-      case 5 * 4 + 1: return ring8_any<T, 5, 4, 64, 1>(a, st);
-      case 5 * 4 + 2: return ring8_any<T, 5, 4, 64, 2>(a, st);
-      case 7 * 4 + 1: return ring8_any<T, 7, 4, 64, 1>(a, st);
-      case 7 * 4 + 2: return ring8_any<T, 7, 4, 64, 2>(a, st);
-    }
+// runtime (element type, cout tile) and tile geometry -> template arguments: f(T{}, IC<CO_T>{}) / f(IC<GEO>{})
+template <typename F>
+static int with_elem_co(int xdt, int co_t, F&& f) {
+  if (xdt == GLSDET_F16) return co_t == 128 ? f(f16{}, IC<128>{}) : f(f16{}, IC<64>{});
+  return co_t == 128 ? f(float{}, IC<128>{}) : f(float{}, IC<64>{});
+}
+template <typename F>
+static int with_geo(int geo, F&& f) {
+  return geo == 1 ? f(IC<1>{}) : (geo == 2 ? f(IC<2>{}) : f(IC<0>{}));
+}
+
+template <typename T, int RING, int KB, int GEO8>
+static int halo_ring8_by_ks(const ConvArgs& a, hipStream_t st) {
+  switch (a.R) {
+    case 3: return ring8_any<T, 3, RING, KB, GEO8>(a, st);
+    case 5: return ring8_any<T, 5, RING, KB, GEO8>(a, st);
+    case 7: return ring8_any<T, 7, RING, KB, GEO8>(a, st);
   }
-  GLS_FAIL(GLSDET_E_ARG, "conv2d(halo ring8): unsupported kernel size %d / geometry %d", a.R, geo);
+  GLS_FAIL(GLSDET_E_ARG, "conv2d(halo ring8): unsupported kernel size %d", a.R);
+}
+template <typename T, int GEO8>
+static int halo_ring8_any(const ConvArgs& a, bool k64, hipStream_t st) {
+  if (k64) return halo_ring8_by_ks<T, 4, 64, GEO8>(a, st);
+  // the other tile geometries: 64-byte channel chunks only (the form the tuner picks at 100 x 168)
+  if constexpr (GEO8 == 0) return halo_ring8_by_ks<T, 3, 128, 0>(a, st);
+  GLS_FAIL(GLSDET_E_ARG, "conv2d(halo ring8): tile geometry %d exists for 64-byte chunks only", GEO8);
 }
 
 // (the chained 1x1 exists for 3x3 stride 1 only: a CSP Bottleneck's conv2 -> the next Bottleneck's conv1)
@@ -926,11 +930,8 @@ static int launch_halo_ring(const ConvArgs& a, hipStream_t st) {
     attr_lds = want_attr;
   }
   ConvArgs b = a;
-  b.n_co_tiles = (a.Cout + CO_T - 1) / CO_T;
-  const int tiles_x = (a.Wo + TileGeo<GEO>::TW - 1) / TileGeo<GEO>::TW, tiles_y = (a.Ho + TileGeo<GEO>::TH - 1) / TileGeo<GEO>::TH;
-  gls_fastdiv(b.n_co_tiles, &b.nco_mul, &b.nco_sh);
-  gls_fastdiv(tiles_x, &b.tx_mul, &b.tx_sh);
-  gls_fastdiv(tiles_y, &b.ty_mul, &b.ty_sh);
+  int tiles_x, tiles_y;
+  fill_halo_tiles<CO_T, TileGeo<GEO>::TH, TileGeo<GEO>::TW>(b, &tiles_x, &tiles_y);
   const long grid = (long)b.n_co_tiles * tiles_x * tiles_y * a.N;
   if (grid <= 0 || grid > 0x7fffffffL) GLS_FAIL(GLSDET_E_ARG, "conv2d(halo ring): grid %ld out of range", grid);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, b, tiles_x, tiles_y);
@@ -964,12 +965,7 @@ static int launch_halo_ring_multi(const ConvArgsN& m0, hipStream_t st) {
   for (int i = 0; i < m.n; ++i) {
     ConvArgs& b = m.p[i];
     b = m0.p[i];
-    b.n_co_tiles = (b.Cout + CO_T - 1) / CO_T;
-    m.tx[i] = (b.Wo + TileGeo<GEO>::TW - 1) / TileGeo<GEO>::TW;
-    m.ty[i] = (b.Ho + TileGeo<GEO>::TH - 1) / TileGeo<GEO>::TH;
-    gls_fastdiv(b.n_co_tiles, &b.nco_mul, &b.nco_sh);
-    gls_fastdiv(m.tx[i], &b.tx_mul, &b.tx_sh);
-    gls_fastdiv(m.ty[i], &b.ty_mul, &b.ty_sh);
+    fill_halo_tiles<CO_T, TileGeo<GEO>::TH, TileGeo<GEO>::TW>(b, &m.tx[i], &m.ty[i]);
     m.start[i] = (int)grid;
     grid += (long)b.n_co_tiles * m.tx[i] * m.ty[i] * b.N;
   }
@@ -980,16 +976,46 @@ static int launch_halo_ring_multi(const ConvArgsN& m0, hipStream_t st) {
   return 0;
 }
 
-// The grouped form of the ring kernel for glsdet_conv2d_multi: hints 8 / 9 (128-byte channel chunks, 64- / 128-row cout
-// tiles; stride 1) and 10 / 11 (64-byte chunks; stride 1 and 2), 3x3 only, no chained / GroupNorm forms.
+// The ring kernels that are compiled, by (chunk size, stride, kernel size) of the problem:
+//   stride 1, 128-byte chunks: 3x3 on every geometry, 5x5 / 7x7 on 8 x 16 tiles only
+//   stride 1, 64-byte chunks:  3x3 / 5x5 / 7x7 on every geometry (ring of four)
+//   stride 2 (3x3, 64-byte chunks, the de-interleaved patch): every geometry
+template <typename T, int CO_T, int GEO>
+static int halo_ring_any(const ConvArgs& a, bool k64, hipStream_t st) {
+  if (a.stride == 2) return launch_halo_ring<T, T, CO_T, 3, 4, 64, 2, false, false, GEO>(a, st);
+  if (k64) {
+    switch (a.R) {
+      case 3: return launch_halo_ring<T, T, CO_T, 3, 4, 64, 1, false, false, GEO>(a, st);
+      case 5: return launch_halo_ring<T, T, CO_T, 5, 4, 64, 1, false, false, GEO>(a, st);
+      case 7: return launch_halo_ring<T, T, CO_T, 7, 4, 64, 1, false, false, GEO>(a, st);
+    }
+  } else {
+    if (a.R == 3) return launch_halo_ring<T, T, CO_T, 3, 3, 128, 1, false, false, GEO>(a, st);
+    if constexpr (GEO == 0) {
+      switch (a.R) {
+        case 5: return launch_halo_ring<T, T, CO_T, 5, CO_T == 64 ? 4 : 3>(a, st);   // 64 rows: a fourth slot costs no workgroup per CU
+        case 7: return launch_halo_ring<T, T, CO_T, 7, CO_T == 64 ? 4 : 3>(a, st);
+      }
+    }
+  }
+  GLS_FAIL(GLSDET_E_ARG, "conv2d(halo ring): no kernel for size %d on tile geometry %d with %d-byte chunks", a.R, GEO, k64 ? 64 : 128);
+}
+// ... and of the grouped form (3x3 only)
+template <typename T, int CO_T, int GEO>
+static int halo_ring_multi_any(const ConvArgsN& m, bool k64, hipStream_t st) {
+  if (m.p[0].stride == 2) return launch_halo_ring_multi<T, T, CO_T, 4, 64, 2, GEO>(m, st);
+  if (k64) return launch_halo_ring_multi<T, T, CO_T, 4, 64, 1, GEO>(m, st);
+  return launch_halo_ring_multi<T, T, CO_T, 3, 128, 1, GEO>(m, st);
+}
+
+// The grouped form of the ring kernel for glsdet_conv2d_multi: 128-byte channel chunks (stride 1) or 64-byte chunks
+// (stride 1 and 2) on 64- / 128-row cout tiles, 3x3 only, no chained / GroupNorm forms.
 // Returns 1 when it does not apply, 0 when `op` (name + launch) was filled in.
-int conv_halo_multi_try(const ConvArgsN& m, int xdt, int ydt, int hint_in, OpRecord* op) {
-  const int geo = (hint_in >= 0x100 && hint_in < 0x300) ? (hint_in >> 8) : 0;       // tile geometry: 8 x 16 / 10 x 12 / 6 x 21
-  const int hint = geo ? (hint_in & 0xff) : hint_in;
-  if (hint < 8 || hint > 11 || xdt != ydt) return 1;
-  if (geo && m.p[0].stride != 1 && !(hint_in & 2)) return 1;         // stride 2: 64-byte chunks (hints 10 / 11)
+int conv_halo_multi_try(const ConvArgsN& m, int xdt, int ydt, const TileHint& hint, OpRecord* op) {
+  if (!hint.ring() || xdt != ydt) return 1;
   const int es = dtype_size(xdt);
-  const bool k64 = hint >= 10;
+  const bool k64 = hint.k64;
+  const int geo = hint.geo;
   const ConvArgs& a0 = m.p[0];
   for (int i = 0; i < m.n; ++i) {
     const ConvArgs& a = m.p[i];
@@ -998,8 +1024,8 @@ int conv_halo_multi_try(const ConvArgsN& m, int xdt, int ydt, int hint_in, OpRec
     if ((a.Cin * es) % (k64 ? 64 : 128)) return 1;
   }
   if (a0.stride == 2 && !k64) return 1;                 // the de-interleaved-patch form exists for 64-byte chunks
-  if ((hint == 9 || hint == 11) && a0.cout_pad <= 64) return 1;
-  const int co_t = (hint == 9 || hint == 11) ? 128 : 64;
+  if (hint.co_pref == 128 && a0.cout_pad <= 64) return 1;
+  const int co_t = hint.co_pref;
   const int str = a0.stride;
   char nm[112];
   int gth, gtw;
@@ -1007,51 +1033,12 @@ int conv_halo_multi_try(const ConvArgsN& m, int xdt, int ydt, int hint_in, OpRec
   snprintf(nm, sizeof nm, "conv_halo_ring%s%s_multi[%d]<%s,%dx%dx%d> 3x3 s%d cin%d cout%d", k64 ? "_k64" : "", str == 2 ? "_s2" : "", m.n,
            xdt ? "f32" : "f16", co_t, gth, gtw, str, a0.Cin, a0.Cout);
   op->name = nm;
-  op->launch = [m, co_t, xdt, k64, str, geo](hipStream_t st) -> int {
-#define GLS_HMG(T_, G_)                                                                                             \
-    if (geo == G_ && str == 2)                                                                                      \
-      return co_t == 128 ? launch_halo_ring_multi<T_, T_, 128, 4, 64, 2, G_>(m, st) : launch_halo_ring_multi<T_, T_, 64, 4, 64, 2, G_>(m, st); \
-    if (geo == G_) {                                                                                                \
-      if (k64) return co_t == 128 ? launch_halo_ring_multi<T_, T_, 128, 4, 64, 1, G_>(m, st) : launch_halo_ring_multi<T_, T_, 64, 4, 64, 1, G_>(m, st); \
-      return co_t == 128 ? launch_halo_ring_multi<T_, T_, 128, 3, 128, 1, G_>(m, st) : launch_halo_ring_multi<T_, T_, 64, 3, 128, 1, G_>(m, st);        \
-    }
-#define GLS_HM(T_)                                                                                                  \
-    GLS_HMG(T_, 1)                                                                                                  \
-    GLS_HMG(T_, 2)                                                                                                  \
-    if (str == 2) return co_t == 128 ? launch_halo_ring_multi<T_, T_, 128, 4, 64, 2>(m, st) : launch_halo_ring_multi<T_, T_, 64, 4, 64, 2>(m, st); \
-    if (k64) return co_t == 128 ? launch_halo_ring_multi<T_, T_, 128, 4, 64, 1>(m, st) : launch_halo_ring_multi<T_, T_, 64, 4, 64, 1>(m, st);      \
-    return co_t == 128 ? launch_halo_ring_multi<T_, T_, 128, 3, 128, 1>(m, st) : launch_halo_ring_multi<T_, T_, 64, 3, 128, 1>(m, st);
-    if (xdt == GLSDET_F16) { GLS_HM(f16) }
-    GLS_HM(float)
-#undef GLS_HM
-#undef GLS_HMG
+  op->launch = [m, co_t, xdt, k64, geo](hipStream_t st) -> int {
+    return with_elem_co(xdt, co_t, [&](auto t, auto co) {
+      return with_geo(geo, [&](auto g) { return halo_ring_multi_any<decltype(t), decltype(co)::value, decltype(g)::value>(m, k64, st); });
+    });
   };
   return 0;
-}
-
-// the other tile geometries (GEO 1 = 10 x 12, 2 = 6 x 21): 128-byte chunks for 3x3 only, 64-byte chunks for 3x3 / 5x5 / 7x7
-template <typename T, typename TO, int CO_T, int GEO>
-static int halo_ring_geo(const ConvArgs& a, bool k64, hipStream_t st) {
-  if (!k64) {
-    if (a.R == 3) return launch_halo_ring<T, TO, CO_T, 3, 3, 128, 1, false, false, GEO>(a, st);
-    GLS_FAIL(GLSDET_E_ARG, "conv2d(halo ring): tile geometry %d with 128-byte chunks exists for 3x3 only", GEO);
-  }
-  switch (a.R) {
-    case 3: return launch_halo_ring<T, TO, CO_T, 3, 4, 64, 1, false, false, GEO>(a, st);
-    case 5: return launch_halo_ring<T, TO, CO_T, 5, 4, 64, 1, false, false, GEO>(a, st);
-    case 7: return launch_halo_ring<T, TO, CO_T, 7, 4, 64, 1, false, false, GEO>(a, st);
-  }
-  GLS_FAIL(GLSDET_E_ARG, "conv2d(halo ring): unsupported kernel size %d", a.R);
-}
-
-template <typename T, typename TO, int CO_T>
-static int halo_ring_by_ks(const ConvArgs& a, hipStream_t st) {
-  switch (a.R) {
-    case 3: return launch_halo_ring<T, TO, CO_T, 3, 3>(a, st);
-    case 5: return launch_halo_ring<T, TO, CO_T, 5, CO_T == 64 ? 4 : 3>(a, st);   // 64 rows: a fourth slot costs no workgroup per CU
-    case 7: return launch_halo_ring<T, TO, CO_T, 7, CO_T == 64 ? 4 : 3>(a, st);
-  }
-  GLS_FAIL(GLSDET_E_ARG, "conv2d(halo ring): unsupported kernel size %d", a.R);
 }
 
 template <typename T, typename TO, int CO_T, int WCO, int KS, int TH, int TW, bool CH = false>
@@ -1074,11 +1061,8 @@ static int launch_halo(const ConvArgs& a, hipStream_t st) {
     attr_lds = want_attr;
   }
   ConvArgs b = a;
-  b.n_co_tiles = (a.Cout + CO_T - 1) / CO_T;
-  const int tiles_x = (a.Wo + TW - 1) / TW, tiles_y = (a.Ho + TH - 1) / TH;
-  gls_fastdiv(b.n_co_tiles, &b.nco_mul, &b.nco_sh);
-  gls_fastdiv(tiles_x, &b.tx_mul, &b.tx_sh);
-  gls_fastdiv(tiles_y, &b.ty_mul, &b.ty_sh);
+  int tiles_x, tiles_y;
+  fill_halo_tiles<CO_T, TH, TW>(b, &tiles_x, &tiles_y);
   const long grid = (long)b.n_co_tiles * tiles_x * tiles_y * a.N;
   if (grid <= 0 || grid > 0x7fffffffL) GLS_FAIL(GLSDET_E_ARG, "conv2d(halo): grid %ld out of range", grid);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, b, tiles_x, tiles_y);
@@ -1096,51 +1080,45 @@ static int halo_by_ks(const ConvArgs& a, hipStream_t st) {
   GLS_FAIL(GLSDET_E_ARG, "conv2d(halo): unsupported kernel size %d", a.R);
 }
 
-template <typename T, typename TO, int CO_T>
-static int halo_ring_k64_by_ks(const ConvArgs& a, hipStream_t st) {
-  switch (a.R) {
-    case 3: return launch_halo_ring<T, TO, CO_T, 3, 4, 64>(a, st);
-    case 5: return launch_halo_ring<T, TO, CO_T, 5, 4, 64>(a, st);
-    case 7: return launch_halo_ring<T, TO, CO_T, 7, 4, 64>(a, st);
-  }
-  GLS_FAIL(GLSDET_E_ARG, "conv2d(halo ring): unsupported kernel size %d", a.R);
-}
-
 // Returns 1 when the halo kernel does not apply (caller falls back to the generic kernel),
 // 0 when `op` was filled in.
-int conv_halo_try(const ConvArgs& a, int xdt, int ydt, int hint_in, OpRecord* op) {
-  // tile geometry in bits 8..9 of a ring hint (8..13): 0x1xx = 10 x 12 (ring8: 10 x 24), 0x2xx = 6 x 21 (ring8: 6 x 42)
-  const int geo = (hint_in >= 0x100 && hint_in < 0x300) ? (hint_in >> 8) : 0;
-  const int hint = geo ? (hint_in & 0xff) : hint_in;
-  if (geo && (hint < 8 || hint > 13)) return 1;
-  if (hint == 12 || hint == 13) {      // 8-wave 128 x 256 form of the ring kernel (13: 64-byte channel chunks)
-    const int es8 = dtype_size(xdt);
+int conv_halo_try(const ConvArgs& a, int xdt, int ydt, const TileHint& hint, OpRecord* op) {
+  const int geo = hint.geo;                 // ring / ring8 hints only (decode_tile_hint)
+  const int es = dtype_size(xdt);
+  if (hint.family == TileHint::RING8) {      // 8-wave 128 x 256 form of the ring kernel
+    const bool k64 = hint.k64;
     if (a.w2 || a.res || a.gn_part || xdt != ydt || a.stride != 1 || a.R != a.S || (a.R != 3 && a.R != 5 && a.R != 7) || a.pad != a.R / 2 ||
-        a.cout_pad <= 64 || (a.Cin * es8) % (hint == 13 ? 64 : 128))
+        a.cout_pad <= 64 || (a.Cin * es) % (k64 ? 64 : 128))
       return 1;
-    const bool k64 = hint == 13;
-    if (geo && !k64) return 1;
     int gth, gtw;
     tile_geo8_dims(geo, &gth, &gtw);
     char nm8[96];
     snprintf(nm8, sizeof nm8, "conv_halo_ring8%s<%s,128x%dx%d> %dx%d s1 cin%d cout%d", k64 ? "_k64" : "", xdt ? "f32" : "f16", gth, gtw, a.R, a.S, a.Cin, a.Cout);
     op->name = nm8;
     op->launch = [a, xdt, k64, geo](hipStream_t st) -> int {
-      return xdt == GLSDET_F16 ? halo_ring8_dispatch<f16>(a, k64, geo, st) : halo_ring8_dispatch<float>(a, k64, geo, st);
+      return with_geo(geo, [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        return xdt == GLSDET_F16 ? halo_ring8_any<f16, G>(a, k64, st) : halo_ring8_any<float, G>(a, k64, st);
+      });
     };
     return 0;
   }
-  if (hint == 1 || hint == 3 || (hint > 5 && hint != 8 && hint != 9 && hint != 10 && hint != 11)) return 1;          // hint 1 / explicit tile = the generic kernel
-  const int es = dtype_size(xdt);
+  const bool automatic = hint.family == TileHint::AUTO;       // may still leave the choice to the generic kernel; a hint forces the halo kernel
+  const bool ring = hint.ring();                    // weight tiles by LDS-DMA into a ring of 64- / 128-row cout tiles,
+  const bool ring_k64 = ring && hint.k64;           // ... with 64-byte channel chunks
+  const bool wpriv = hint.family == TileHint::HALO_WPRIV;      // wave-private weight staging (128-row cout tile only)
+  if (!automatic && !ring && !wpriv && hint.family != TileHint::HALO && hint.family != TileHint::HALO_64) return 1;   // another kernel family
   if (a.w2 && (a.R != 3 || a.stride != 1)) return 1;      // chained 1x1: compiled into the 3x3 stride-1 forms only
-  if (a.gn_part && (a.R != 3 || a.stride != 1 || hint < 8 || hint > 11 || a.w2 || a.res)) return 1;   // GN partials: ring forms only
+  if (a.gn_part && (a.R != 3 || a.stride != 1 || !ring || a.w2 || a.res)) return 1;   // GN partials: ring forms only
   if (geo && (a.w2 || a.gn_part)) return 1;
+  if (hint.co_pref == 128 && a.cout_pad <= 64) return 1;
+  // wasted MFMA work on partial tiles: prefer the flat-pixel kernel when it is large
+  const long tiles = (long)((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);
+  const bool wasteful = (double)tiles * 128.0 / ((double)a.Ho * a.Wo) > 1.30;
   if (a.stride == 2) {            // 3x3 stride 2: the de-interleaved-patch form of the ring kernel, 64-byte channel chunks
-    if (a.R != 3 || a.S != 3 || a.pad != 1 || xdt != ydt || (a.Cin * es) % 64 || (hint != 0 && hint != 10 && hint != 11)) return 1;
-    if (hint == 11 && a.cout_pad <= 64) return 1;
-    const long tiles = (long)((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);
-    if (hint == 0 && (double)tiles * 128.0 / ((double)a.Ho * a.Wo) > 1.30) return 1;
-    const int co_t = (a.cout_pad <= 64 || hint != 11) ? 64 : 128;      // measured: 64-row tiles win unless the tuner says otherwise
+    if (a.R != 3 || a.S != 3 || a.pad != 1 || xdt != ydt || (a.Cin * es) % 64 || !(automatic || ring_k64)) return 1;
+    if (automatic && wasteful) return 1;
+    const int co_t = (a.cout_pad <= 64 || hint.co_pref != 128) ? 64 : 128;      // measured: 64-row tiles win unless the tuner says otherwise
     if (a.w2 && a.c2_0 / co_t != (a.c2_0 + a.cin2 - 1) / co_t) return 1;
     char nm[96];
     int sth, stw;
@@ -1148,29 +1126,19 @@ int conv_halo_try(const ConvArgs& a, int xdt, int ydt, int hint_in, OpRecord* op
     snprintf(nm, sizeof nm, "conv_halo_ring_k64_s2<%s,%dx%dx%d> 3x3 s2 cin%d cout%d%s", xdt ? "f32" : "f16", co_t, sth, stw, a.Cin, a.Cout, a.w2 ? " +1x1" : "");
     op->name = nm;
     op->launch = [a, co_t, xdt, geo](hipStream_t st) -> int {
-#define GLS_S2(T_, G_)                                                                                                                  \
-      if (geo == G_) return co_t == 128 ? launch_halo_ring<T_, T_, 128, 3, 4, 64, 2, false, false, G_>(a, st)                               \
-                                        : launch_halo_ring<T_, T_, 64, 3, 4, 64, 2, false, false, G_>(a, st);
-      if (xdt == GLSDET_F16) { GLS_S2(f16, 1) GLS_S2(f16, 2) } else { GLS_S2(float, 1) GLS_S2(float, 2) }
-#undef GLS_S2
-      if (xdt == GLSDET_F16) return co_t == 128 ? launch_halo_ring<f16, f16, 128, 3, 4, 64, 2>(a, st) : launch_halo_ring<f16, f16, 64, 3, 4, 64, 2>(a, st);
-      return co_t == 128 ? launch_halo_ring<float, float, 128, 3, 4, 64, 2>(a, st) : launch_halo_ring<float, float, 64, 3, 4, 64, 2>(a, st);
+      return with_elem_co(xdt, co_t, [&](auto t, auto co) {
+        return with_geo(geo, [&](auto g) { return halo_ring_any<decltype(t), decltype(co)::value, decltype(g)::value>(a, true, st); });
+      });
     };
     return 0;
   }
   if (a.stride != 1 || a.R != a.S || (a.R != 3 && a.R != 5 && a.R != 7) || a.pad != a.R / 2) return 1;
-  if ((a.Cin * es) % ((hint == 10 || hint == 11) ? 64 : 128)) return 1;      // whole channel chunks (hint 10 works on 64-byte chunks)
+  if ((a.Cin * es) % (ring_k64 ? 64 : 128)) return 1;      // whole channel chunks
   if (xdt != ydt) return 1;
-  if (geo && !((hint == 8 || hint == 9) ? a.R == 3 : (hint == 10 || hint == 11))) return 1;
-  // wasted MFMA work on partial tiles: prefer the flat-pixel kernel when it is large
-  const long tiles = (long)((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);
-  const double waste = (double)tiles * 128.0 / ((double)a.Ho * a.Wo);
-  if (hint != 2 && hint != 4 && hint != 5 && (hint < 8 || hint > 11) && waste > 1.30) return 1;      // a hint forces the halo kernel
-  const bool ring = hint >= 8 && hint <= 11;       // weight tiles by LDS-DMA into a ring: 8 = 64-row, 9 = 128-row cout tiles,
-  const bool ring_k64 = hint == 10 || hint == 11;  // 10 / 11 = 64- / 128-row tiles with 64-byte channel chunks
-  if ((hint == 9 || hint == 11) && a.cout_pad <= 64) return 1;
-  const int co_t = (a.cout_pad <= 64 || hint == 5 || hint == 8 || hint == 10) ? 64 : 128;     // hint 5 / 8 / 10: 64-row cout tiles also for wide layers
-  const bool wpriv = hint == 4;                     // wave-private weight staging (128-row cout tile only)
+  if (geo && !ring_k64 && a.R != 3) return 1;       // the other geometries with 128-byte chunks: 3x3 only
+  if (automatic && wasteful) return 1;
+  // HALO_64 and the 64-row ring hints: 64-row cout tiles also for wide layers
+  const int co_t = (a.cout_pad <= 64 || hint.family == TileHint::HALO_64 || hint.co_pref == 64) ? 64 : 128;
   if (wpriv && co_t != 128) return 1;
   if (a.w2 && a.c2_0 / co_t != (a.c2_0 + a.cin2 - 1) / co_t) return 1;      // chained 1x1: its input channels in ONE cout tile
   char nm[96];
@@ -1180,28 +1148,17 @@ int conv_halo_try(const ConvArgs& a, int xdt, int ydt, int hint_in, OpRecord* op
            a.S, a.Cin, a.Cout, a.w2 ? " +1x1" : "");
   op->name = nm;
   op->launch = [a, co_t, xdt, wpriv, ring, ring_k64, geo](hipStream_t st) -> int {
-    if (geo == 1) {
-      if (xdt == GLSDET_F16) return co_t == 128 ? halo_ring_geo<f16, f16, 128, 1>(a, ring_k64, st) : halo_ring_geo<f16, f16, 64, 1>(a, ring_k64, st);
-      return co_t == 128 ? halo_ring_geo<float, float, 128, 1>(a, ring_k64, st) : halo_ring_geo<float, float, 64, 1>(a, ring_k64, st);
-    }
-    if (geo == 2) {
-      if (xdt == GLSDET_F16) return co_t == 128 ? halo_ring_geo<f16, f16, 128, 2>(a, ring_k64, st) : halo_ring_geo<f16, f16, 64, 2>(a, ring_k64, st);
-      return co_t == 128 ? halo_ring_geo<float, float, 128, 2>(a, ring_k64, st) : halo_ring_geo<float, float, 64, 2>(a, ring_k64, st);
-    }
-    if (ring_k64) {
-      if (xdt == GLSDET_F16) return co_t == 128 ? halo_ring_k64_by_ks<f16, f16, 128>(a, st) : halo_ring_k64_by_ks<f16, f16, 64>(a, st);
-      return co_t == 128 ? halo_ring_k64_by_ks<float, float, 128>(a, st) : halo_ring_k64_by_ks<float, float, 64>(a, st);
-    }
-    if (ring) {
-      if (xdt == GLSDET_F16) return co_t == 128 ? halo_ring_by_ks<f16, f16, 128>(a, st) : halo_ring_by_ks<f16, f16, 64>(a, st);
-      return co_t == 128 ? halo_ring_by_ks<float, float, 128>(a, st) : halo_ring_by_ks<float, float, 64>(a, st);
-    }
-    if (wpriv) return xdt == GLSDET_F16 ? halo_by_ks<f16, f16, 128, 4>(a, st) : halo_by_ks<float, float, 128, 4>(a, st);
-    if (xdt == GLSDET_F16) return co_t == 128 ? halo_by_ks<f16, f16, 128, 2>(a, st) : halo_by_ks<f16, f16, 64, 2>(a, st);
-    return co_t == 128 ? halo_by_ks<float, float, 128, 2>(a, st) : halo_by_ks<float, float, 64, 2>(a, st);
+    return with_elem_co(xdt, co_t, [&](auto t, auto co) -> int {
+      typedef decltype(t) T;
+      constexpr int CO_T = decltype(co)::value;
+      if (ring) return with_geo(geo, [&](auto g) { return halo_ring_any<T, CO_T, decltype(g)::value>(a, ring_k64, st); });
+      if constexpr (CO_T == 128) {
+        if (wpriv) return halo_by_ks<T, T, 128, 4>(a, st);
+      }
+      return halo_by_ks<T, T, CO_T, 2>(a, st);
+    });
   };
   return 0;
 }
 
 }  // namespace glsdet
-

@@ -83,15 +83,28 @@ typedef struct glsdet_conv_desc {
   const float* scale;
   const float* bias;
   int32_t R, S, stride, pad, act;
-  int32_t tile_hint;       /* 0 auto | 1 generic | 2 halo (s1 kxk) | 4 halo, wave-private weights | 5 halo, 64-row cout tiles |
-                            * 8 / 9 halo with the weight tiles in an LDS-DMA ring (64- / 128-row cout tiles) | 10 / 11 the same with
-                            *   64-byte channel chunks (64 / 128 rows) | 12 / 13 the 8-wave form: 128 cout rows x 8 x 32 pixels per
-                            *   512-thread workgroup (128- / 64-byte chunks; no residual) | 3 weight-stationary 1x1 |
-                            * 0x100 | h, 0x200 | h (h = 8..11, 13): ring kernel h on 10 x 12 resp. 6 x 21 pixel tiles (h = 13:
-                            *   10 x 24 resp. 6 x 42) instead of 8 x 16 (8 x 32) -- fewer wasted lanes on 50 x 84 / 25 x 42 maps |
-                            * 16..31 the persistent LDS-DMA 1x1 kernel, variant hint - 16 (csrc/conv_gemm.hip: tile, ring
-                            *   depth, K panel, weight-resident, single shot) |
-                            * co_tile<<16|px_tile (|0x8000: 64-byte K steps); 128<<16|0 = the 8-wave 128 x 256 tile */
+  int32_t tile_hint;       /* which kernel runs the conv.  This table is the authority: csrc/conv_common.h decodes it once
+                            * (decode_tile_hint) and every entry point refuses, with GLSDET_E_ARG when the op is built, a
+                            * value that is not listed here -- nothing is recorded that could only fail at launch.
+                            *   family   0 automatic | 1 generic kernel, tile chosen by the library | 2 halo kernel (stride-1
+                            *            k x k) | 3 weight-stationary 1x1 | 4 halo, wave-private weight staging | 5 halo,
+                            *            64-row cout tiles also for wide layers | 8..11 halo with the weight tiles in an
+                            *            LDS-DMA ring | 12 / 13 its 8-wave form: 128 cout rows x 8 x 32 pixels per 512-thread
+                            *            workgroup (no residual) | 16..31 the persistent LDS-DMA 1x1 kernel
+                            *            (6 / 7, a persistent halo kernel, no longer exist)
+                            *   cout tile  8, 10: 64 rows | 9, 11: 128 rows
+                            *   k64      10, 11, 13: 64-byte channel chunks (8, 9, 12: 128-byte)
+                            *   geometry 0x100 | h, 0x200 | h (h = 8..11, 13 only): ring kernel h on 10 x 12 resp. 6 x 21
+                            *            pixel tiles (h = 13: 10 x 24 resp. 6 x 42) instead of 8 x 16 (8 x 32) -- fewer
+                            *            wasted lanes on 50 x 84 / 25 x 42 maps
+                            *   variant  16 + v, v = 0..15: row v of the table in csrc/conv_gemm.hip (tile, ring depth,
+                            *            K panel, weight-resident, single shot)
+                            *   tile     co << 16 | px: the generic kernel on a co x px tile -- 128x128, 64x128, 32x128,
+                            *            64x64, and 128 << 16 | 0 = the 8-wave 128 x 256 tile (Cin a whole number of K
+                            *            steps, no chained conv); glsdet_conv2d_multi has 128x128, 64x128, 64x64 only
+                            *            (32x128 runs as 64x64; its batched form also 128x256 as 128x128)
+                            *   kb64     bit 15 of a tile: 64-byte K steps
+                            *   dbg      bits 8..10 of a tile: diagnostic switches (timing experiments; results invalid) */
 } glsdet_conv_desc;
 
 int     glsdet_conv2d(const glsdet_conv_desc* d, void* stream);
