@@ -20,6 +20,11 @@ allocated by the op on the input's device, nothing synchronises.  There is no CP
             -> (dets [N,max_det,7], count [2N], status [1])
         py_cpu_softnms / batched_soft_nms, drone/merge_results.py:41-130; cand fp32 [N, cap, 8] rows x1,y1,x2,y2,score,label,
         counts int32 [N]; method 1 linear, 2 gaussian, 3 hard; dets rows x1,y1,x2,y2, original score, decayed score, label
+    glsdet::ufp_pack(dets, counts, expand, img_w, img_h) -> (chips f64 [N,max_det,7], chips_floor f32 [N,max_det,7],
+            header f64 [N,4], status int32 [N])
+        UnifiedForegroundPacking, ufp/UFPMP-Det-Tools/ufp/unified_foreground_packing.py:6-197 + spp.py:77-168, on the coarse
+        detector's rows: dets fp32 [N, max_det, 7] x1,y1,x2,y2,score,score,label, counts int32 [N] (or the detector's [2N]);
+        chip rows src_x,src_y,w,h,canvas_x,canvas_y,magnification; header n_boxes,n_chips,canvas_w,canvas_h
     glsdet::batched_nms(boxes, scores, idxs, iou_threshold) -> keep int64 [K]
         torchvision.ops.boxes.batched_nms's signature (utils_bbox.py:414-419), one image
 
@@ -97,6 +102,7 @@ def register():
                    "(Tensor, Tensor, Tensor)")
     lib_def.define("soft_nms(Tensor cand, Tensor counts, int num_classes, int method, float iou_thr, float sigma, "
                    "float min_score, bool rescore, int max_det) -> (Tensor, Tensor, Tensor)")
+    lib_def.define("ufp_pack(Tensor dets, Tensor counts, float expand, int img_w, int img_h) -> (Tensor, Tensor, Tensor, Tensor)")
     lib_def.define("batched_nms(Tensor boxes, Tensor scores, Tensor idxs, float iou_threshold) -> Tensor")
     impl = torch.library.Library("glsdet", "IMPL", "CUDA")
     cpu = torch.library.Library("glsdet", "IMPL", "CPU")
@@ -206,6 +212,28 @@ def register():
         return (cand.new_empty((n, max_det, 7)), cand.new_empty((2 * n,), dtype=torch.int32),
                 cand.new_empty((1,), dtype=torch.int32))
 
+    # ------------------------------------------------------------------ ufp_pack
+    def ufp_pack(dets, counts, expand, img_w, img_h):
+        lib = _lib.load()
+        _need_cuda(dets, counts)
+        if dets.dtype != torch.float32 or not dets.is_contiguous() or dets.dim() != 3 or dets.shape[2] != 7:
+            raise RuntimeError("ufp_pack: dets must be a contiguous fp32 [N, max_det, 7] tensor")
+        n, max_det = dets.shape[0], dets.shape[1]
+        if counts.dtype != torch.int32 or not counts.is_contiguous() or counts.numel() not in (n, 2 * n):
+            raise RuntimeError("ufp_pack: counts must be a contiguous int32 [N] (or the detector's [2N]) tensor")
+        chips = torch.zeros(n, max_det, 7, dtype=torch.float64, device=dets.device)
+        chips_floor = torch.zeros(n, max_det, 7, dtype=torch.float32, device=dets.device)
+        header = torch.zeros(n, 4, dtype=torch.float64, device=dets.device)
+        status = torch.zeros(n, dtype=torch.int32, device=dets.device)
+        check(lib.glsdet_ufp_pack(dets.data_ptr(), counts.data_ptr(), n, max_det, expand, img_w, img_h, chips.data_ptr(),
+                                  chips_floor.data_ptr(), header.data_ptr(), status.data_ptr(), _stream(dets)), "ufp_pack")
+        return chips, chips_floor, header, status
+
+    def ufp_pack_meta(dets, counts, expand, img_w, img_h):
+        n, max_det = dets.shape[0], dets.shape[1]
+        return (dets.new_empty((n, max_det, 7), dtype=torch.float64), dets.new_empty((n, max_det, 7)),
+                dets.new_empty((n, 4), dtype=torch.float64), dets.new_empty((n,), dtype=torch.int32))
+
     # ------------------------------------------------------------------ batched_nms (torchvision's signature)
     def batched_nms(boxes, scores, idxs, iou_threshold):
         _need_cuda(boxes, scores, idxs)
@@ -230,7 +258,7 @@ def register():
 
     for name, fn, fm in (("conv_bn_act", conv_bn_act, conv_bn_act_meta), ("nonlocal_dot", nonlocal_dot, lambda x, *a: torch.empty_like(x)),
                          ("yolox_decode", yolox_decode, yolox_decode_meta), ("nms", nms, nms_meta),
-                         ("soft_nms", soft_nms, soft_nms_meta),
+                         ("soft_nms", soft_nms, soft_nms_meta), ("ufp_pack", ufp_pack, ufp_pack_meta),
                          ("batched_nms", batched_nms, lambda b, s, i, t: b.new_empty((0,), dtype=torch.int64))):
         impl.impl(name, fn)
         cpu.impl(name, no_cpu)

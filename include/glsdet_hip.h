@@ -586,6 +586,52 @@ int glsdet_ufp_backmap_merge(const float* dets, const int32_t* count, int32_t ma
                              float* out, int32_t* out_count, int32_t* status, void* ws, int64_t ws_bytes,
                              void* stream);
 
+/* Unified foreground packing on the device (an additive export of ABI 17): ufp/UFPMP-Det-Tools/ufp/unified_foreground_packing.py:6-197
+ * (scale_boxes :6-32, ForegroundRegionGeneration :54-87, Packing :125-164) and spp.py:77-168 (phsppog sorted by height,
+ * recursive_packing) on the coarse detector's own buffers, so that only `header` crosses the bus between the two stages.
+ * One wave per image; no host synchronisation and no allocation inside the call: legal under stream capture.
+ *   dets / count : fp32 [n_img][max_det][7] rows x1,y1,x2,y2,score,score,label in the detector's NMS order and int32
+ *                  [n_img] (glsdet_gfl_detect's buffers).  Rows at and beyond the count are not read.
+ *   The result is that of UnifiedForegroundPacking(boxes_class_major_float32, expand, [img_w, img_h]) under numpy 2
+ *   (NEP 50), where a float32 input makes the computation mixed precision:
+ *     order     : class-major, stable (np.argsort(labels, kind="stable")); within a class the detector's order.
+ *     enlarge   : float32, each operation rounded once: half_w = ((x2-x1)*0.5f)*expand (expand rounded to float32 first),
+ *                 cx = (x2+x1)*0.5f, clip of cx -/+ half_w to [0, img_w-1] (ties give the bound), y alike.  The object
+ *                 area (x2-x1+1)*(y2-y1+1) is float32 and is accumulated in float32.
+ *     merge     : float32.  For i ascending, if alive, for j ascending over every alive j != i (earlier j included): the
+ *                 union box by min / max; merge iff (ux1-ux0)*(uy1-uy0) < (r2-r0)*(r3-r1) + (o2-o0)*(o3-o1), each product and
+ *                 the sum rounded on their own (no fused multiply-add).  The region grows as soon as a j merges: later j see
+ *                 the grown region, earlier j are not revisited.
+ *     magnify   : (double)area_sum / (double)count, an IEEE float64 division; < 1024 -> 4, < 9216 -> 2, else 1.
+ *     sizes     : (double)(float)(r2-r0) * magnification; from here on everything is float64 (strip width, width - w,
+ *                 top + h, x + rw and the equality tests).
+ *     strip     : rectangles by decreasing height, stable.  The first unplaced one opens a shelf at (0, top) and leaves the
+ *                 slot (w, top, width - w, h); a slot takes the FIRST rectangle of the lowest class among 1 exact fit,
+ *                 2 exact width, 3 exact height, 4 strictly smaller both ways, else it dies.  Class 2 leaves the slot above,
+ *                 class 3 the slot to the right; class 4 compares with `smallest`, the least side of the rectangles still
+ *                 unplaced AFTER the pick (infinity when none): w-rw < smallest: above (full width); h-rh < smallest: right
+ *                 (full height); rw < smallest: right (height rh), then above (full width); else above (width rw), then right
+ *                 (full height).  The first slot is filled completely before the second.
+ *     bisection : lo = 300, hi = 2666, mid = (lo+hi)/2, lo = mid+1 when the packed height > mid else hi = mid-1, while
+ *                 lo <= hi: 11 probes.  The layout of the LAST probe is used, feasible or not.
+ *     claim     : placed rectangles in region order; each claims every still-pending region of exactly equal magnified
+ *                 size, in ascending region order, at its own position (equal-sized regions share one position).
+ *   chips       : fp64 [n_img][max_det][7] = src_x, src_y, w, h, canvas_x, canvas_y, magnification, in claim order; rows at
+ *                 and beyond n_chips are not written.
+ *   chips_floor : fp32, (float)floor(chips): what glsdet_ufp_mosaic / glsdet_ufp_backmap_merge take.
+ *   header      : fp64 [n_img][4] = n_boxes, n_chips, canvas_w, canvas_h (max of x+w / y+h over the placed rectangles).
+ *   status      : int32 [n_img], written for every image; bit0 = count outside [0, max_det]: then the header row is
+ *                 count, 0, 0, 0 (n_boxes holds the count as it was read) and no chip is written.
+ *   glsdet_ufp_pack_max_boxes() = (160 KiB - 32) / 104 = 1575: per box the LDS holds the region (16 bytes), four doubles
+ *                 (size and position, 32), a stack slot (32, plus one slot of 32 bytes per image), area sum and count (8)
+ *                 and four int32 maps and flags (16).
+ *   Refused on the host: null or misaligned pointers (4 bytes; chips / header 8), n_img < 1, max_det outside
+ *   1 .. glsdet_ufp_pack_max_boxes(), expand not finite or <= 0, img_w < 1 or img_h < 1.                                   */
+int32_t glsdet_ufp_pack_max_boxes(void);
+int glsdet_ufp_pack(const float* dets, const int32_t* count, int32_t n_img, int32_t max_det, float expand,
+                    int32_t img_w, int32_t img_h, double* chips, float* chips_floor, double* header, int32_t* status,
+                    void* stream);
+
 /* ---------------------------------------------------------------------------------
  * bbox COCOeval: COCOeval.computeIoU + evaluateImg
  * (drone/models/core/cocoeval.py:163-190, 235-313; the protocol ufp/ufpmp_det_eval.py:333-338 runs

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Latency of the two-stage UFPMP-Det path for ONE 540x1024 frame (synthetic weights): coarse GFL at
-1333x800 -> host packing -> device mosaic -> fine MPDet -> device back-mapping + merge NMS."""
+1333x800 -> host packing -> device mosaic -> fine MPDet -> device back-mapping + merge NMS; then the throughput of the
+pipelined forms, and a same-process A/B of packing="host" against packing="device" (glsdet_ufp_pack) at one, two and
+three lanes with the pack kernel's own time from HIP events.  --packing-only skips the middle part."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -50,6 +52,80 @@ print("two-stage, one 540x1024 frame: %.2f ms end to end (%.1f frames/s); host p
          tuple(x2.shape), sum(len(m) for m in merged)))
 
 frames = [synth_image((540, 1024), 100 + i)[:, :, ::-1].copy() for i in range(8)] * 4
+
+
+def packing_ab():
+    """frames/s of both packing modes, interleaved in one process; results must be identical"""
+    pl = {(w, m): TwoStagePipeline(coarse, fine, stage, c1, c2, workers=w, packing=m) for w in (1, 2, 3) for m in ("host", "device")}
+    for (w, m), p in pl.items():
+        p.run(frames[:8] * w)                # every lane sees every shape once
+    torch.cuda.synchronize()
+    ref = None
+    for rep in range(3):
+        line = []
+        for (w, m), p in pl.items():
+            t0 = time.perf_counter()
+            out = p.run(frames)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            ref = out if ref is None else ref
+            same = all(all(np.array_equal(a, b) for a, b in zip(x, y)) for x, y in zip(ref, out))
+            line.append("%d lane%s %s %.1f%s" % (w, "s" if w > 1 else "", m, len(frames) / dt, "" if same else " (RESULTS DIFFER)"))
+        print("packing A/B, 32 frames, frames/s: " + "; ".join(line))
+    for m in ("host", "device"):
+        for _ in range(3):
+            two_stage_detect(coarse, fine, img, stage, c1, c2, packing=m)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(20):
+            two_stage_detect(coarse, fine, img, stage, c1, c2, packing=m)
+        torch.cuda.synchronize()
+        print("sequential two_stage_detect, packing=%s: %.2f ms per frame" % (m, (time.perf_counter() - t0) / 20 * 1e3))
+
+
+def pack_kernel_time():
+    """glsdet_ufp_pack alone, HIP events around 20 launches: the bench frame's coarse buffers, then max_det at the limit"""
+    from glsdet_amd import _lib
+    lib = _lib.load()
+    _, dmid = two_stage_detect(coarse, fine, img, stage, c1, c2, packing="device")
+    nb = dmid["coarse_compiled"].nb
+    limit = int(lib.glsdet_ufp_pack_max_boxes())
+    rng = np.random.default_rng(0)
+    cases = [("bench frame", nb["dets"][0].clone(), nb["count"][:1].clone(), 1024, 540)]
+    for name, lo, hi in (("limit, overlapping boxes of 6..220 px", 6, 220), ("limit, sparse boxes of 4..40 px", 4, 40)):
+        c = rng.uniform(0, 1, (limit, 2)) * [1920, 1080]
+        wh = np.exp(rng.uniform(np.log(lo), np.log(hi), (limit, 2)))
+        d = np.zeros((limit, 7), np.float32)
+        d[:, :4] = np.clip(np.concatenate([c - wh / 2, c + wh / 2], 1), 0, [1919, 1079, 1919, 1079])
+        d[:, 6] = rng.integers(0, 10, limit)
+        cases.append((name, torch.from_numpy(d).cuda(), torch.tensor([limit], dtype=torch.int32).cuda(), 1920, 1080))
+    for name, dets, count, W, H in cases:
+        n = int(dets.shape[0])
+        exact = torch.empty(n, 7, dtype=torch.float64, device="cuda")
+        floor = torch.empty(n, 7, dtype=torch.float32, device="cuda")
+        header = torch.empty(4, dtype=torch.float64, device="cuda")
+        status = torch.empty(1, dtype=torch.int32, device="cuda")
+
+        def launch():
+            _lib.check(lib.glsdet_ufp_pack(dets.data_ptr(), count.data_ptr(), 1, n, 1.5, W, H, exact.data_ptr(), floor.data_ptr(),
+                                           header.data_ptr(), status.data_ptr(), torch.cuda.current_stream().cuda_stream), "ufp_pack")
+        for _ in range(3):
+            launch()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            launch()
+        e1.record()
+        e1.synchronize()
+        h = header.cpu().tolist()
+        print("glsdet_ufp_pack, %s: %d boxes -> %d chips, canvas %g x %g, %.1f us per launch (max_det %d)"
+              % (name, h[0], h[1], h[2], h[3], e0.elapsed_time(e1) / 20 * 1e3, n))
+
+
+if "--packing-only" in sys.argv:
+    packing_ab()
+    pack_kernel_time()
+    sys.exit(0)
 pipes = {g: TwoStagePipeline(coarse, fine, stage, c1, c2, use_graph=g) for g in (False, True)}
 for g in (False, True):                     # warm: plans (and graphs) for the mosaic shapes of these frames
     for f in frames[:8]:
@@ -76,3 +152,5 @@ for rep in range(2):
         same = all(all(np.array_equal(a, b) for a, b in zip(x, y)) for x, y in zip(ref, out))
         line.append("%s %.1f%s" % (name, len(frames) / dt, "" if same else " (RESULTS DIFFER)"))
     print("32 frames, frames/s: " + "; ".join(line))
+packing_ab()
+pack_kernel_time()
