@@ -33,6 +33,10 @@ class HipDetector:
     def compile(self, n: int, H: int, W: int, post: Optional[dict] = None, use_graph: bool = False,
                 instance: int = 0) -> _Compiled:
         """post: None (raw logits only) or dict(conf_thres, nms_thres, max_cand, max_det, mode, sigmoid, exchange_cap);
+        max_cand = NMS candidates kept per image, default min(4096, A) (A = anchors of the input shape); more passing
+        anchors than that make collect() raise.  max_cand = A can never overflow and costs an A * ceil(A / 64) * 8 byte
+        suppression mask per image (9 MB at A = 8400, 61 MB at A = 22050) in the plan's workspace; at most 32768.
+        max_det = rows of the result per image, default 1000.
         sigmoid = the decode's sigmoid mask (bit 0 objectness, bit 1 classes; default 3 = both, see DECODE_MODES);
         exchange_cap = K appends the multi-GPU exchange record ([n, K+1, 7], Engine.pack_detections) to the plan.
         `instance` > 0 builds an independent copy (own buffers, own stream) of the same plan, so
@@ -129,15 +133,29 @@ class HipDetector:
         self.run(c, img.to(c.img.device, torch.float32))
         return [l.to_nchw(5 + self.num_classes) for l in c.levels]
 
-    def detect(self, img: torch.Tensor, conf_thres: float, nms_thres: float, max_det: int = 1000, mode: int = 0,
-               decode_mode: str = "default"):
+    @staticmethod
+    def num_anchors(H: int, W: int) -> int:
+        """anchors of an H x W input: one per cell of the stride 8, 16 and 32 levels"""
+        return sum((H // s) * (W // s) for s in (8, 16, 32))
+
+    def detect(self, img: torch.Tensor, conf_thres: float, nms_thres: float, max_det: Optional[int] = None, mode: int = 0,
+               decode_mode: str = "default", max_cand: Optional[int] = None):
         """-> (decoded [B,A,5+nc] device tensor, list per image of ndarray(k,7) [x1,y1,x2,y2,obj,cls_conf,cls])
+        max_cand / max_det: NMS candidates / result rows per image; None = all A anchors, so no confidence threshold
+        can overflow them (the reference is scored at 0.01 and 0.0001, where nearly every anchor is a candidate).  That
+        costs an A * ceil(A / 64) * 8 byte mask per image in the plan's workspace (about 61 MB at A = 22050); where the
+        scenes are known to be sparse pass a smaller max_cand, e.g. max_cand=4096 keeps the whole NMS in the
+        class-segmented kernels with a 2 MB mask.  More candidates than max_cand, or more detections than max_det, raise.
         decode_mode: the reference harness's name (drone/yolo.py:75-82) for the score channels that get a sigmoid --
         'default' | 'obj_sigmoid' | 'no_sigmoid' | 'cls_sigmoid'; the others reach the NMS as raw logits."""
         if decode_mode not in DECODE_MODES:
             raise ValueError("decode_mode must be one of %s (got %r)" % (sorted(DECODE_MODES), decode_mode))
         n, _, H, W = img.shape
-        post = dict(conf_thres=conf_thres, nms_thres=nms_thres, max_det=max_det, mode=mode)
+        A = self.num_anchors(H, W)
+        if A > 32768 and max_cand is None:
+            raise ValueError("a %dx%d input has %d anchors; the NMS takes at most 32768 candidates per image: pass max_cand" % (H, W, A))
+        post = dict(conf_thres=conf_thres, nms_thres=nms_thres, max_det=A if max_det is None else max_det, mode=mode,
+                    max_cand=A if max_cand is None else max_cand)
         if DECODE_MODES[decode_mode] != 3:          # the default keeps the plan-cache key it always had
             post["sigmoid"] = DECODE_MODES[decode_mode]
         c = self.compile(n, H, W, post)

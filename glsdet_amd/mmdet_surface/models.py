@@ -321,8 +321,11 @@ class YOLOX(nn.Module):
         det = self._detector()
         img = img.to("cuda", torch.float32)
         n, _, H, W = img.shape
-        post = dict(conf_thres=float(cfg["score_thr"]), nms_thres=float(cfg["nms"]["iou_threshold"]),
-                    max_det=H // 8 * (W // 8) + H // 16 * (W // 16) + H // 32 * (W // 32), mode=1, rescale=bool(rescale))
+        # all-anchor capacity: at the config's score_thr = 0.01 nearly every anchor is an NMS candidate (the mask costs
+        # A * ceil(A / 64) * 8 bytes per image, see HipDetector.detect)
+        A = HipDetector.num_anchors(H, W)
+        post = dict(conf_thres=float(cfg["score_thr"]), nms_thres=float(cfg["nms"]["iou_threshold"]), max_cand=A, max_det=A,
+                    mode=1, rescale=bool(rescale))
         c = det.compile(n, H, W, post)
         scale = None
         if rescale:

@@ -838,14 +838,20 @@ class HipGflDetector:
         return [l.to_nchw(self.num_classes) for l in c.cls], [l.to_nchw(bins) for l in c.reg]
 
     def detect(self, img: torch.Tensor, score_thr: float = 0.05, iou_thr: float = 0.6, nms_pre: int = 1000,
-               max_per_img: int = 100, img_shapes=None, scale_factors=None, use_graph: bool = False, instance: int = 0):
+               max_per_img: int = 100, img_shapes=None, scale_factors=None, use_graph: bool = False, instance: int = 0,
+               max_cand: Optional[int] = None):
         """-> list per image of (dets ndarray(k,5) x1,y1,x2,y2,score ; labels ndarray(k) int64).
+        max_cand: (position, class) pairs above score_thr kept per level and image before the nms_pre cut; None = 8192.
+        A level with more passing pairs raises; H_l * W_l * num_classes (at most 32768) can never overflow and costs 48
+        bytes per pair and level.
         use_graph: replay a hipGraph captured for this (batch, H, W, thresholds) -- one plan per input shape
         stays resident (the fine stage of UFPMP-Det sees a few dozen padded mosaic shapes; at ~0.5 GB of
         activations each they all fit the HBM many times over)."""
         n, _, H, W = img.shape
         post = dict(score_thr=score_thr, iou_thr=iou_thr, nms_pre=nms_pre, max_per_img=max_per_img,
                     rescale=scale_factors is not None)
+        if max_cand is not None:                 # None keeps the plan-cache key (and the 8192 default of compile)
+            post["max_cand"] = int(max_cand)
         c = self.compile(n, H, W, post, use_graph=use_graph, instance=instance)   # instance: private buffers per caller thread
         hw = None if img_shapes is None else torch.tensor([[s[0], s[1]] for s in img_shapes], dtype=torch.float32)
         sf = None if scale_factors is None else torch.tensor(np.asarray(scale_factors, np.float32).reshape(n, 4))
@@ -857,7 +863,8 @@ class HipGflDetector:
     def collect(c: _Compiled):
         count = c.nb["count"].cpu().numpy()              # the one host sync of the path
         if int(c.nb["status"].item()) & 1:
-            raise RuntimeError("GFL candidate capacity exceeded on a level (raise max_cand)")
+            raise RuntimeError("GFL candidate capacity exceeded on a level: more than max_cand=%d (position, class) pairs "
+                               "pass score_thr (raise it: detect(..., max_cand=...) or post['max_cand'])" % c.nb["max_cand"])
         dets = c.nb["dets"].cpu().numpy()
         n = c.nb["n"]
         out = []

@@ -166,7 +166,7 @@ def clusters(rng, m, spread=1.0):
 def chain(m, thr, per_row=220):
     """Stepped chains: box i + 1 is box i shifted right by d; IoU(i, i+1) > thr >= IoU(i, i+2), so in index order
     i suppresses i + 1, which then cannot suppress i + 2: the kept set alternates and the dependency chain is as long
-    as the row (per_row boxes, rows two units apart and disjoint)."""
+    as the row (per_row boxes, rows two units apart and disjoint; 1.5 units apart once two would leave the grid)."""
     d = 0.25
     assert thr < 1.0
     w = None
@@ -178,7 +178,8 @@ def chain(m, thr, per_row=220):
     if w is None:                                      # thr = 0: every overlapping pair suppresses; use touching steps
         w = 2 * d
     i = np.arange(m)
-    x, y = (i % per_row) * d, (i // per_row) * 2.0
+    step = 2.0 if ((m - 1) // per_row) * 2.0 + 1 < GRID else 1.5       # the boxes are 1 high: rows stay disjoint
+    x, y = (i % per_row) * d, (i // per_row) * step
     assert x.max(initial=0) + w < GRID and y.max(initial=0) + 1 < GRID
     return np.stack([x, y, x + w, y + 1.0], 1).astype(F32)
 
@@ -188,11 +189,13 @@ def identical(m):
 
 
 def disjoint(m):
-    """m boxes in distinct cells of a 128 x 128 lattice (cell 1/2, box 3/8): no pair overlaps; neighbours do not touch."""
-    assert m <= 128 * 127
+    """m boxes in distinct cells of a 128 x 128 lattice (cell 1/2, box 3/8): no pair overlaps; neighbours do not touch.
+    Above 128 * 127 boxes the lattice is 256 x 256 (cell 1/4, box 3/16)."""
+    side, cell = (128, 0.5) if m <= 128 * 127 else (256, 0.25)
+    assert m <= side * (side - 1)
     i = np.arange(m)
-    x, y = (i % 128) * 0.5, (i // 128) * 0.5
-    return np.stack([x, y, x + 0.375, y + 0.375], 1).astype(F32)
+    x, y = (i % side) * cell, (i // side) * cell
+    return np.stack([x, y, x + 0.75 * cell, y + 0.75 * cell], 1).astype(F32)
 
 
 def exact_threshold_pairs(m, thr, rng):
@@ -256,12 +259,14 @@ TIE_TABLE = (64, 100, 128, 200, 255)                   # k / 256; 64 / 256 == CO
 def build_scores(kind, m, rng):
     """-> (obj [m], conf [m]) float32 with obj * conf exact and >= CONF_THR.
     distinct: a random permutation of m different values; desc: different values falling with the index;
-    few: a handful of values from TIE_TABLE (half of the low ones as 0.5 * 2s); equal: all 0.5."""
+    few: a handful of values from TIE_TABLE (half of the low ones as 0.5 * 2s); equal: all 0.5.
+    Above 8192 candidates distinct / desc take their values from k / 65536, k in [16384, 65536): 16 bits, still exact."""
     obj = np.ones(m, F32)
+    assert m <= 49152
     if kind == "distinct":
-        conf = (4096 + rng.permutation(8192)[:m]) / 16384.0
+        conf = (4096 + rng.permutation(8192)[:m]) / 16384.0 if m <= 8192 else (16384 + rng.permutation(49152)[:m]) / 65536.0
     elif kind == "desc":
-        conf = (4096 + 8191 - np.arange(m)) / 16384.0
+        conf = (4096 + 8191 - np.arange(m)) / 16384.0 if m <= 8192 else (65535 - np.arange(m)) / 65536.0
     elif kind == "few":
         conf = rng.choice(TIE_TABLE, m) / 256.0
         half = (conf <= 0.5) & (rng.integers(0, 2, m) == 1)
@@ -271,7 +276,6 @@ def build_scores(kind, m, rng):
         conf = np.full(m, 0.5)
     else:
         raise KeyError(kind)
-    assert m <= 8192
     return obj, conf.astype(F32)
 
 
@@ -367,9 +371,47 @@ A_DEFAULT = 6000                                       # not a multiple of 64
 MIXED = (0, 5000, 70, 4096, 4097, 1)                   # both kernel families write into one dets / count buffer
 
 
-def _case(cid, ms, A=A_DEFAULT, nc=80, mode=1, thr=0.5, **kw):
-    """kw: struct / layout / scores (one value for all images), seed"""
-    return dict(id=cid, ms=tuple(ms), A=A, nc=nc, mode=mode, thr=thr, kw=kw)
+DENSE_COUNTS = (8192, 8193, 8400, 22050, 32767, 32768)   # every anchor a candidate: 128, 129, 132, 345, 512, 512 mask words
+DENSE_A = 8400                                         # a 640 x 640 input; 22050 = the benchmark's 800 x 1344
+DENSE_MIXED = (8400, 0, 4097, 70, 4096)                # one launch, max_cand = 8400: the per-image flags pick the family
+NMS_MAX = 32768                                        # GLS_NMS_MAXW * 64: the kernels refuse more candidates per image
+
+
+def _case(cid, ms, A=A_DEFAULT, nc=80, mode=1, thr=0.5, cap=None, **kw):
+    """kw: struct / layout / scores (one value for all images), seed.  cap: max_cand = max_det of the GPU run
+    (None: the 8192 of tests/test_post_fuzz.py)"""
+    return dict(id=cid, ms=tuple(ms), A=A, nc=nc, mode=mode, thr=thr, cap=cap, kw=kw)
+
+
+def dense_cases():
+    """The regime of the reference's evaluation thresholds (confidence 0.01 / 0.0001): every anchor is a candidate, up to
+    the kernels' limit of 32768.  A = m (but for one case), max_cand = max_det = A.  At 22050 and above the candidates
+    are spread over 40 of 80 classes so that the CPU pair check stays at some 10^7 pairs; rank / mask / scan rank and
+    scan all m rows whatever the classes.  The largest single-class cases have 8400 candidates."""
+    cs = []
+    for i, m in enumerate(DENSE_COUNTS):
+        if m in (22050, 32768):
+            continue
+        cs.append(_case("dense_count%d" % m, [m], A=m, cap=m, mode=i % 2, layout="populated:40",
+                        scores=("distinct", "few")[i % 2], seed=100 + i))
+    for j, m in enumerate((22050, 32768)):
+        cs.append(_case("dense_clusters_%d" % m, [m], A=m, cap=m, mode=j, layout="populated:40", seed=110 + j))
+        cs.append(_case("dense_disjoint_%d" % m, [m], A=m, cap=m, mode=1 - j, thr=0.65, struct="disjoint", layout="populated:40",
+                        scores="few", seed=112 + j))
+    cs.append(_case("dense_nc256_32768", [32768], A=32768, cap=32768, nc=256, mode=0, layout="populated:40", scores="few", seed=114))
+    cs.append(_case("dense_A9000_m8400", [8400], A=9000, cap=9000, mode=0, thr=0.65, layout="populated:40", seed=115))
+    A = DENSE_A
+    cs.append(_case("dense_chain_one_class", [A], A=A, cap=A, struct="chain", layout="single:7", scores="desc", seed=120))
+    cs.append(_case("dense_identical_one_class", [A], A=A, cap=A, mode=0, struct="identical", layout="single:79", seed=121))
+    cs.append(_case("dense_identical_balanced", [A], A=A, cap=A, struct="identical", scores="few", seed=122))
+    cs.append(_case("dense_exact_thr0.5", [A], A=A, cap=A, mode=0, thr=0.5, struct="exact", layout="populated:3", nc=10, seed=123))
+    cs.append(_case("dense_exact_thr0.65", [A], A=A, cap=A, thr=0.65, struct="exact", layout="populated:3", nc=10, seed=124))
+    cs.append(_case("dense_ties_all_equal", [A], A=A, cap=A, scores="equal", nc=4, seed=125))
+    cs.append(_case("dense_ties_few", [A], A=A, cap=A, mode=0, scores="few", nc=4, seed=126))
+    cs.append(_case("dense_ties_equal_chain", [A], A=A, cap=A, struct="chain", layout="single:0", scores="equal", nc=4, seed=127))
+    cs.append(_case("dense_mixed", DENSE_MIXED, A=A, cap=A, scores="few", nc=10, seed=128))
+    cs.append(_case("dense_mixed_distinct_mode0", DENSE_MIXED, A=A, cap=A, mode=0, thr=0.65, seed=129))
+    return cs
 
 
 def nms_cases():
@@ -413,6 +455,7 @@ def nms_cases():
     cs.append(_case("A8191", [5000], A=8191, nc=10, mode=0, seed=61))
     cs.append(_case("A8191_full", [8191], A=8191, nc=10, struct="disjoint", scores="few", seed=62))
     cs.append(_case("A33_n3", [33, 1, 20], A=33, nc=2, seed=63))
+    cs += dense_cases()
     ids = [c["id"] for c in cs]
     assert len(set(ids)) == len(ids)
     return cs

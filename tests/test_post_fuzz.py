@@ -6,7 +6,8 @@ NMS is compared BIT FOR BIT with the naive sequential reference of tests/post_re
 the inputs lie on a dyadic grid on which the IoU arithmetic is exact up to one correctly rounded division
 (tests/test_post_reference.py proves on the CPU, for every case used here, that the float32 decisions equal the
 exact-arithmetic ones).  The old kernel family is reached through candidate counts above 4096 and num_classes = 256,
-never through an environment switch."""
+never through an environment switch.  The dense cases (post_reference.dense_cases) run it where every anchor is a
+candidate, up to the 32768 rows the kernels accept, with max_cand = max_det = A."""
 import numpy as np
 import pytest
 import torch
@@ -73,7 +74,8 @@ def _run_nms(eng, nbcache, pred, nc, mode, thr, max_det=MAX_CAND, max_cand=MAX_C
 @pytest.mark.parametrize("case", NMS_CASES, ids=[c["id"] for c in NMS_CASES])
 def test_nms_equals_the_sequential_reference(engines, nbcache, case):
     pred, _ = R.build_case(case)
-    _run_nms(engines["f32"], nbcache, pred, case["nc"], case["mode"], case["thr"])
+    cap = case["cap"] or MAX_CAND
+    _run_nms(engines["f32"], nbcache, pred, case["nc"], case["mode"], case["thr"], max_det=cap, max_cand=cap)
 
 
 @pytest.mark.parametrize("m", [4095, 4096])
@@ -84,15 +86,17 @@ def test_nms_full_workspace_of_4096_has_no_second_path(engines, nbcache, m):
     _run_nms(engines["f32"], nbcache, pred, 10, 0, 0.65, max_det=4096, max_cand=4096)
 
 
-@pytest.mark.parametrize("m", [1000, 5000], ids=["class_segmented", "rank_mask_scan"])
+@pytest.mark.parametrize("m", [1000, 5000, R.DENSE_A], ids=["class_segmented", "rank_mask_scan", "every_anchor_of_8400"])
 def test_nms_max_det_around_the_kept_count(engines, nbcache, m):
-    """max_det in {1, 64, K - 1, K, K + 1}: count[i] = min(K, max_det), count[n + i] = K, the first max_det rows"""
-    pred = R.to_pred([R.build_image(R.A_DEFAULT, 10, m, scores="few", seed=70)], 10, 1)
+    """max_det in {1, 64, K - 1, K, K + 1}: count[i] = min(K, max_det), count[n + i] = K, the first max_det rows.
+    m = 8400: A = max_cand = m, every anchor a candidate."""
+    A, cap = (R.A_DEFAULT, MAX_CAND) if m < R.A_DEFAULT else (m, m)
+    pred = R.to_pred([R.build_image(A, 10, m, scores="few", seed=70)], 10, 1)
     ref = R.reference_dets(pred[0], 10, 1, 0.5)
     K = len(ref)
     assert 64 < K < m
     for md in (1, 64, K - 1, K, K + 1):
-        _run_nms(engines["f32"], nbcache, pred, 10, 1, 0.5, max_det=md, refs=[ref])
+        _run_nms(engines["f32"], nbcache, pred, 10, 1, 0.5, max_det=md, max_cand=cap, refs=[ref])
 
 
 def test_nms_workspace_reuse_and_determinism(engines):
@@ -110,14 +114,15 @@ def test_nms_workspace_reuse_and_determinism(engines):
         assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
-@pytest.mark.parametrize("m,max_cand", [(500, 64), (5000, 4096), (6000, 4097)])
+@pytest.mark.parametrize("m,max_cand", [(500, 64), (5000, 4096), (6000, 4097), (9000, 8400)])
 def test_nms_overflow_is_flagged_and_returns_input_rows(engines, m, max_cand):
     """more candidates than max_cand: status bit 1, count <= max_det, every returned row is a row of the input.  (Which
     candidates are retained depends on their arrival order, by design: nothing more is asserted.)"""
     eng = engines["f32"]
-    pred = R.to_pred([R.build_image(R.A_DEFAULT, 10, m, scores="few", seed=90)], 10, 1)
+    A = max(R.A_DEFAULT, m)
+    pred = R.to_pred([R.build_image(A, 10, m, scores="few", seed=90)], 10, 1)
     rows = {tuple(x) for x in R.candidates(pred[0], 10, 1)["rows"].tolist()}
-    nb = eng.nms_buffers(1, R.A_DEFAULT, max_cand, 300)
+    nb = eng.nms_buffers(1, A, max_cand, 300)
     dets, count, status = eng.nms(torch.from_numpy(pred).cuda(), 10, 1, R.CONF_THR, 0.5, nb)
     torch.cuda.synchronize()
     count = count.cpu().numpy()
@@ -125,6 +130,48 @@ def test_nms_overflow_is_flagged_and_returns_input_rows(engines, m, max_cand):
     assert 0 < count[0] <= 300 and count[0] <= count[1] <= max_cand
     for row in dets[0, : count[0]].cpu().numpy().tolist():
         assert tuple(row) in rows
+
+
+def _layout_bytes(n, max_cand, with_mask=True):
+    """nms_layout of post.hip restated in Python integers: every array rounded up to 256 bytes; the mask holds
+    ceil(max_cand / 64) 8-byte words per candidate"""
+    nw = (max_cand + 63) // 64
+    parts = [n * 8] + [n * max_cand * k for k in (16, 16, 4, 4, 16, 16)]
+    parts += [n * max_cand * nw * 8] if with_mask else []
+    parts += [n * max_cand * 8, n * (256 + 256 + 260 + 260) * 4]
+    return sum((p + 255) // 256 * 256 for p in parts)
+
+
+@pytest.mark.parametrize("n,max_cand", [(1, R.NMS_MAX), (1, R.NMS_MAX - 1), (3, 22050), (2, 8400), (32, R.NMS_MAX)])
+def test_nms_workspace_bytes_equals_the_layout_sum(engines, n, max_cand):
+    """the n * max_cand * nw * 8 byte mask dominates: 128 MiB for one image of 32768 candidates, 4 GiB for 32 of them
+    (above 2^31 and 2^32: a product taken in 32 bits would show).  Only the size is asked for; nothing is allocated."""
+    want = _layout_bytes(n, max_cand)
+    assert want > n * max_cand * ((max_cand + 63) // 64) * 8
+    if (n, max_cand) == (1, R.NMS_MAX):
+        assert want - _layout_bytes(n, max_cand, False) == 128 << 20
+    if n == 32:
+        assert want > 1 << 32
+    assert int(engines["f32"].lib.glsdet_nms_workspace_bytes(n, max_cand, max_cand)) == want
+
+
+def test_nms_refuses_more_than_32768_candidates_on_the_host(engines):
+    """max_cand = 32769 is an argument error (GLSDET_E_ARG = -1) whose text names the limit; the check comes before the op
+    is built, so nothing is launched: the outputs keep their sentinel values.  32768 with the same buffers is accepted
+    up to the workspace check (GLSDET_E_CAPACITY = -5: the 256-byte workspace is too small), again without a launch."""
+    lib = engines["f32"].lib
+    pred = torch.zeros(1, 64, 6).cuda()
+    dets, count = torch.full((1, 4, 7), -7.0).cuda(), torch.full((2,), -7, dtype=torch.int32).cuda()
+    status, ws = torch.full((1,), -7, dtype=torch.int32).cuda(), torch.zeros(512, dtype=torch.uint8).cuda()
+    wsp = (ws.data_ptr() + 255) // 256 * 256
+    call = lambda mc: lib.glsdet_nms(pred.data_ptr(), 1, 64, 1, 1, 0.25, 0.5, mc, 4, dets.data_ptr(), count.data_ptr(),
+                                     status.data_ptr(), wsp, 256, None)
+    assert call(R.NMS_MAX + 1) == -1
+    msg = lib.glsdet_last_error().decode()
+    assert "32768" in msg and "32769" in msg, msg
+    assert call(R.NMS_MAX) == -5
+    torch.cuda.synchronize()
+    assert (dets == -7.0).all() and (count == -7).all() and int(status.item()) == -7
 
 
 # ------------------------------------------------------------------------------------------------ gfl_detect
@@ -141,6 +188,13 @@ GFL_CASES = [
     dict(id="rm7_nc1", seed=4, nc=1, reg_max=7, thr=0.05, bias=-2.0, nms_pre=1000, iou=0.6, maxdet=3000, rescale=False),
     dict(id="rm7_nc80_cut", seed=5, nc=80, reg_max=7, thr=0.5, bias=-3.0, nms_pre=300, iou=0.6, maxdet=100, rescale=True),
 ]
+GFL_DENSE_CASES = [                                                 # level sizes of their own (the others share GFL_SIZES)
+    # every (position, class) pair passes (sigmoid > 0): 48 * 64 * 10 = 30720 pairs on level 0, beyond the 8192 a level
+    # holds by default; max_cand is sized for them
+    dict(id="rm16_nc10_every_pair_30720_cut", seed=8, nc=10, reg_max=16, thr=0.0, bias=-3.0, nms_pre=1000, iou=0.6, maxdet=3000,
+         rescale=False, sizes=[(48, 64), (24, 32), (12, 16), (6, 8), (3, 4)], input=(384, 512), shapes=[(380, 500, 3), (384, 512, 3)],
+         max_cand=30720),
+]
 
 
 def _gfl_inputs(case, n=2):
@@ -148,20 +202,21 @@ def _gfl_inputs(case, n=2):
     0 and 2 and switched off (-40) at a few others.  Only ONE class is saturated: the oracle orders equal scores of
     different classes class first, the kernels anchor first (tests/test_post_reference.py)."""
     g = torch.Generator().manual_seed(1000 + case["seed"])
-    cls = [torch.randn(n, case["nc"], h, w, generator=g) * 1.5 + case["bias"] for h, w in GFL_SIZES]
-    reg = [torch.randn(n, 4 * (case["reg_max"] + 1), h, w, generator=g) * 2.0 for h, w in GFL_SIZES]
+    sizes = case.get("sizes", GFL_SIZES)
+    cls = [torch.randn(n, case["nc"], h, w, generator=g) * 1.5 + case["bias"] for h, w in sizes]
+    reg = [torch.randn(n, 4 * (case["reg_max"] + 1), h, w, generator=g) * 2.0 for h, w in sizes]
     for l, pos in ((0, [(0, 0), (5, 17), (5, 18), (20, 40), (36, 52)]), (2, [(3, 3), (9, 13)])):
         for b in range(n):
             for y, x in pos:
                 cls[l][b, 0, y, x] = 40.0
-                cls[l][b, 0, (y + 7) % GFL_SIZES[l][0], x] = -40.0
+                cls[l][b, 0, (y + 7) % sizes[l][0], x] = -40.0
     return cls, reg
 
 
 def _gfl_reference(case, cls, reg, dtype):
     """oracle pre-NMS candidates evaluated in `dtype`, then its per-class NMS.  -> per image (boxes, scores, labels, keep)"""
     sf = GFL_SF if case["rescale"] else None
-    pre = M.gfl_pre_nms([c.to(dtype) for c in cls], [r.to(dtype) for r in reg], GFL_STRIDES, GFL_SHAPES, case["thr"],
+    pre = M.gfl_pre_nms([c.to(dtype) for c in cls], [r.to(dtype) for r in reg], GFL_STRIDES, case.get("shapes", GFL_SHAPES), case["thr"],
                         case["nms_pre"], sf, case["reg_max"])
     out = []
     for boxes, scores, labels in pre:
@@ -195,7 +250,7 @@ def _gfl_seed_conditions(case, cls, reg):
     return r32, r64, ncut
 
 
-@pytest.mark.parametrize("case", GFL_CASES, ids=[c["id"] for c in GFL_CASES])
+@pytest.mark.parametrize("case", GFL_CASES + GFL_DENSE_CASES, ids=[c["id"] for c in GFL_CASES + GFL_DENSE_CASES])
 def test_gfl_detect_vs_oracle_generic_integral_saturation_and_cuts(engines, case):
     """glsdet_gfl_detect against oracle.mpdet_oracle (gfl_pre_nms + batched_nms + max_per_img): labels, counts and the
     order are equal; scores to 1e-6 (the existing test's bound); box coordinates to max(1e-3, 2 x the float32 oracle's
@@ -209,12 +264,22 @@ def test_gfl_detect_vs_oracle_generic_integral_saturation_and_cuts(engines, case
     cls, reg = _gfl_inputs(case, n)
     r32, r64, ncut = _gfl_seed_conditions(case, cls, reg)
     assert ncut > 0 or "cut" not in case["id"]                             # a level holds more than nms_pre candidates
-    nb = eng.gfl_buffers(n, 5, 2 * MAX_CAND, case["nms_pre"], case["maxdet"])
-    hw = torch.tensor([[s[0], s[1]] for s in GFL_SHAPES], dtype=torch.float32).cuda()
+    nb = eng.gfl_buffers(n, 5, case.get("max_cand", 2 * MAX_CAND), case["nms_pre"], case["maxdet"])
+    hw = torch.tensor([[s[0], s[1]] for s in case.get("shapes", GFL_SHAPES)], dtype=torch.float32).cuda()
     sft = torch.tensor(GFL_SF, dtype=torch.float32).cuda() if case["rescale"] else None
-    dets, count, status = eng.gfl_detect([_fp32_view(eng, c) for c in cls], [_fp32_view(eng, r) for r in reg], GFL_STRIDES,
-                                         nc, case["reg_max"], GFL_IN[0], GFL_IN[1], case["thr"], case["iou"], nb,
-                                         img_hw=hw, scale_factors=sft)
+    in_h, in_w = case.get("input", GFL_IN)
+    views = [_fp32_view(eng, c) for c in cls], [_fp32_view(eng, r) for r in reg]
+    if "max_cand" in case:
+        # the same input at the default capacity of a level (8192): reported, never a silently truncated result
+        passing = max(int((c[b].sigmoid() > case["thr"]).sum()) for c in cls for b in range(n))
+        assert MAX_CAND < passing <= case["max_cand"]
+        small = eng.gfl_buffers(n, 5, MAX_CAND, case["nms_pre"], case["maxdet"])
+        _, _, st = eng.gfl_detect(views[0], views[1], GFL_STRIDES, nc, case["reg_max"], in_h, in_w, case["thr"], case["iou"], small,
+                                  img_hw=hw, scale_factors=sft)
+        torch.cuda.synchronize()
+        assert int(st.item()) & 1
+    dets, count, status = eng.gfl_detect(views[0], views[1], GFL_STRIDES, nc, case["reg_max"], in_h, in_w, case["thr"],
+                                         case["iou"], nb, img_hw=hw, scale_factors=sft)
     torch.cuda.synchronize()
     assert int(status.item()) == 0
     count, dets = count.cpu().numpy(), dets.cpu().numpy()

@@ -6,6 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import glsdet_oracle as O
+from tests import post_reference as R
 
 
 def test_ops_are_registered_and_have_no_cpu_fallback():
@@ -100,3 +101,45 @@ def test_batched_nms_op_has_torchvisions_contract():
     want = O.batched_nms(boxes, scores, labels.astype(np.float32), 0.5)
     assert keep.dtype == torch.int64 and keep.cpu().tolist() == want.tolist()
     assert torch.ops.glsdet.batched_nms(torch.zeros(0, 4).cuda(), torch.zeros(0).cuda(), torch.zeros(0, dtype=torch.int64).cuda(), 0.5).numel() == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("m", [5000, 9000])
+def test_batched_nms_op_above_4096_boxes(m):
+    """more boxes than the class-segmented kernels take (4096), one class alone holding more than that, and three exact
+    duplicate rows (box, score and class): the lowest index of the three is the one that can survive, and no index comes
+    back twice"""
+    import glsdet_amd.torch_ops  # noqa: F401
+    rng = np.random.default_rng(m)
+    c = rng.uniform(50, 1200, (m, 2))
+    wh = rng.uniform(10, 120, (m, 2))
+    boxes = np.concatenate([c - wh / 2, c + wh / 2], 1).astype(np.float32)
+    scores = rng.uniform(0, 1, m).astype(np.float32)
+    labels = np.where(rng.uniform(0, 1, m) < 0.9, 2, rng.integers(0, 6, m))
+    dup = [7, m // 2, m - 3]
+    scores[dup[0]] = 1.25                                                # above every other: visited first and kept, its two copies suppressed
+    for i in dup[1:]:
+        boxes[i], scores[i], labels[i] = boxes[dup[0]], scores[dup[0]], labels[dup[0]]
+    assert (labels == 2).sum() > 4096 and len(np.unique(labels)) == 6
+    keep = torch.ops.glsdet.batched_nms(torch.from_numpy(boxes).cuda(), torch.from_numpy(scores).cuda(),
+                                        torch.from_numpy(labels).cuda(), 0.5).cpu().numpy()
+    want = O.batched_nms(boxes, scores, labels.astype(np.float32), 0.5)
+    assert keep.dtype == np.int64 and len(np.unique(keep)) == len(keep)
+    assert 1000 < len(want) < m and want[0] == dup[0] and not set(dup[1:]) & set(want.tolist())
+    assert keep.tolist() == want.tolist()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cid", ["dense_count8400", "dense_ties_few"])
+def test_nms_op_with_every_anchor_a_candidate(cid):
+    """A = 8400 (a 640 x 640 input), every anchor passes: the op sizes its workspace for A candidates; rows, order and
+    counts equal the sequential reference bit for bit (exact-arithmetic inputs, tests/post_reference.py)"""
+    import glsdet_amd.torch_ops  # noqa: F401
+    case = next(c for c in R.dense_cases() if c["id"] == cid)
+    pred, _ = R.build_case(case)
+    A, nc = case["A"], case["nc"]
+    dets, count, status = torch.ops.glsdet.nms(torch.from_numpy(pred).cuda(), nc, case["mode"], R.CONF_THR, case["thr"], A)
+    ref = R.reference_dets(pred[0], nc, case["mode"], case["thr"])
+    assert len(R.candidates(pred[0], nc, case["mode"])["anchors"]) == A == 8400
+    assert int(status.item()) == 0 and count.cpu().tolist() == [len(ref), len(ref)]
+    np.testing.assert_array_equal(dets[0, : len(ref)].cpu().numpy(), ref)

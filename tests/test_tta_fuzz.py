@@ -222,9 +222,9 @@ def _run_merge(eng, rows, metas, thr, max_det, out_scale=None, slack=3):
     return dets.cpu().numpy(), count.cpu().numpy()
 
 
-def _check_merge(eng, rows, metas, thr, max_det, out_scale=None):
+def _check_merge(eng, rows, metas, thr, max_det, out_scale=None, slack=3):
     K, n = len(rows), len(rows[0])
-    dets, count = _run_merge(eng, rows, metas, thr, max_det, out_scale)
+    dets, count = _run_merge(eng, rows, metas, thr, max_det, out_scale, slack)
     totals = []
     for b in range(n):
         want, total, keep = T.merge([rows[k][b] for k in range(K)], [metas[k][b] for k in range(K)], thr, max_det,
@@ -281,6 +281,16 @@ def test_aug_merge_nms_around_4096_merged_candidates(eng, total):
     rows, metas = _aug_inputs(total, [[2048], [total - 2048]], [[0], [1]], [[1.0], [2.0]])
     (kept, m, _), = _check_merge(eng, rows, metas, 0.5, 5000)
     assert m == total and 0 < kept < total
+
+
+def test_aug_merge_nms_full_lists_at_the_capacity_limit(eng):
+    """The capacities sum to exactly GLS_NMS_MAXW * 64 = 32768 and every list is full to its last row (no slack): the
+    rank sort, the 512-word mask rows and the scan's shared arrays at their upper limit.  Three augmentations with three
+    scale factors and flips; 40 classes keep the naive reference at some 10^7 pairs."""
+    counts = [[16384], [8192], [8192]]
+    rows, metas = _aug_inputs(32768, counts, [[0], [1], [3]], [[1.0], [2.0], [0.5]], nc=40)
+    (kept, m, _), = _check_merge(eng, rows, metas, 0.5, 32768, slack=0)
+    assert m == 32768 and 4096 < kept < m
 
 
 def test_aug_merge_nms_capacity_limit(eng):
