@@ -25,6 +25,13 @@ allocated by the op on the input's device, nothing synchronises.  There is no CP
         UnifiedForegroundPacking, ufp/UFPMP-Det-Tools/ufp/unified_foreground_packing.py:6-197 + spp.py:77-168, on the coarse
         detector's rows: dets fp32 [N, max_det, 7] x1,y1,x2,y2,score,score,label, counts int32 [N] (or the detector's [2N]);
         chip rows src_x,src_y,w,h,canvas_x,canvas_y,magnification; header n_boxes,n_chips,canvas_w,canvas_h
+    glsdet::voc_ap(dt_box, score, cls_off, pair_off, pair_det, gt_off, gt_box, gt_difficult, n_gt, n_img, min_overlap,
+            fppi_ref, validate=False) -> (tp i32 [T,ND], fp i32 [T,ND], rec f64 [T,ND], prec f64 [T,ND], mpre f64 [T,ND],
+            cls_out f64 [T,C,16])
+        VOC-style mAP, get_map of drone/models/core/utils_map.py:294-813 (matching :474-512, curves :570-617, voc_ap
+        :99-140, the nine picked miss rates of :26-62); the arrays of glsdet_voc_ap in include/glsdet_hip.h, built by
+        glsdet_amd/eval/voc.py.  validate=True reads the offsets back (one synchronisation) and refuses non-monotone
+        offsets or a pair_det that is no permutation; the kernels clamp either way.
     glsdet::batched_nms(boxes, scores, idxs, iou_threshold) -> keep int64 [K]
         torchvision.ops.boxes.batched_nms's signature (utils_bbox.py:414-419), one image
 
@@ -103,6 +110,9 @@ def register():
     lib_def.define("soft_nms(Tensor cand, Tensor counts, int num_classes, int method, float iou_thr, float sigma, "
                    "float min_score, bool rescore, int max_det) -> (Tensor, Tensor, Tensor)")
     lib_def.define("ufp_pack(Tensor dets, Tensor counts, float expand, int img_w, int img_h) -> (Tensor, Tensor, Tensor, Tensor)")
+    lib_def.define("voc_ap(Tensor dt_box, Tensor score, Tensor cls_off, Tensor pair_off, Tensor pair_det, Tensor gt_off, "
+                   "Tensor gt_box, Tensor gt_difficult, Tensor n_gt, Tensor n_img, Tensor min_overlap, Tensor fppi_ref, "
+                   "bool validate=False) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
     lib_def.define("batched_nms(Tensor boxes, Tensor scores, Tensor idxs, float iou_threshold) -> Tensor")
     impl = torch.library.Library("glsdet", "IMPL", "CUDA")
     cpu = torch.library.Library("glsdet", "IMPL", "CPU")
@@ -234,6 +244,54 @@ def register():
         return (dets.new_empty((n, max_det, 7), dtype=torch.float64), dets.new_empty((n, max_det, 7)),
                 dets.new_empty((n, 4), dtype=torch.float64), dets.new_empty((n,), dtype=torch.int32))
 
+    # ------------------------------------------------------------------ voc_ap
+    def _voc_shapes(dt_box, score, cls_off, pair_off, pair_det, gt_off, gt_box, gt_difficult, n_gt, n_img, min_overlap, fppi_ref):
+        nd, ng, C_, P, T = score.numel(), gt_difficult.numel(), cls_off.numel() - 1, pair_off.numel() - 1, min_overlap.numel()
+        for t, dt, shape, what in ((dt_box, torch.float64, (nd, 4), "dt_box fp64 [ND, 4]"), (score, torch.float64, (nd,), "score fp64 [ND]"),
+                                   (cls_off, torch.int32, (C_ + 1,), "cls_off int32 [C+1]"), (pair_off, torch.int32, (P + 1,), "pair_off int32 [P+1]"),
+                                   (pair_det, torch.int32, (nd,), "pair_det int32 [ND]"), (gt_off, torch.int32, (P + 1,), "gt_off int32 [P+1]"),
+                                   (gt_box, torch.float64, (ng, 4), "gt_box fp64 [NG, 4]"),
+                                   (gt_difficult, torch.uint8, (ng,), "gt_difficult uint8 [NG]"), (n_gt, torch.int32, (C_,), "n_gt int32 [C]"),
+                                   (n_img, torch.int32, (C_,), "n_img int32 [C]"), (min_overlap, torch.float64, (T,), "min_overlap fp64 [T]"),
+                                   (fppi_ref, torch.float64, (9,), "fppi_ref fp64 [9]")):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise RuntimeError("voc_ap: %s expected, got %s %s" % (what, t.dtype, tuple(t.shape)))
+        if C_ < 0 or P < 0 or T < 1:
+            raise RuntimeError("voc_ap: offsets need at least one entry and min_overlap at least one threshold")
+        return nd, ng, C_, P, T
+
+    def voc_ap(dt_box, score, cls_off, pair_off, pair_det, gt_off, gt_box, gt_difficult, n_gt, n_img, min_overlap, fppi_ref,
+               validate=False):
+        lib = _lib.load()
+        args = (dt_box, score, cls_off, pair_off, pair_det, gt_off, gt_box, gt_difficult, n_gt, n_img, min_overlap, fppi_ref)
+        _need_cuda(*args)
+        nd, ng, C_, P, T = _voc_shapes(*args)
+        if validate:
+            for t, top, what in ((cls_off, nd, "cls_off"), (pair_off, nd, "pair_off"), (gt_off, ng, "gt_off")):
+                h = t.cpu()
+                if int(h[0]) != 0 or int(h[-1]) != top or bool((h[1:] < h[:-1]).any()):
+                    raise RuntimeError("voc_ap: %s must rise from 0 to %d without a step down" % (what, top))
+            if nd and not torch.equal(torch.sort(pair_det.cpu().long()).values, torch.arange(nd)):
+                raise RuntimeError("voc_ap: pair_det must hold every detection index exactly once")
+        dev = score.device
+        ws = torch.empty(int(lib.glsdet_voc_ap_workspace_bytes(ng, T)), dtype=torch.uint8, device=dev)
+        tp, fp = (torch.zeros(T, nd, dtype=torch.int32, device=dev) for _ in range(2))
+        rec, prec, mpre = (torch.zeros(T, nd, dtype=torch.float64, device=dev) for _ in range(3))
+        cls_out = torch.zeros(T, C_, 16, dtype=torch.float64, device=dev)
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+        if C_ > 0:
+            check(lib.glsdet_voc_ap(ptr(dt_box), ptr(score), cls_off.data_ptr(), nd, C_, pair_off.data_ptr(), ptr(pair_det),
+                                    gt_off.data_ptr(), P, ptr(gt_box), ptr(gt_difficult), ng, n_gt.data_ptr(), n_img.data_ptr(),
+                                    min_overlap.data_ptr(), T, fppi_ref.data_ptr(), ptr(tp), ptr(fp), ptr(rec), ptr(prec), ptr(mpre),
+                                    cls_out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(score)), "voc_ap")
+        return tp, fp, rec, prec, mpre, cls_out
+
+    def voc_ap_meta(dt_box, score, cls_off, pair_off, pair_det, gt_off, gt_box, gt_difficult, n_gt, n_img, min_overlap, fppi_ref,
+                    validate=False):
+        nd, C_, T = score.numel(), cls_off.numel() - 1, min_overlap.numel()
+        i32, f64 = (lambda *s: score.new_empty(s, dtype=torch.int32)), (lambda *s: score.new_empty(s, dtype=torch.float64))
+        return i32(T, nd), i32(T, nd), f64(T, nd), f64(T, nd), f64(T, nd), f64(T, C_, 16)
+
     # ------------------------------------------------------------------ batched_nms (torchvision's signature)
     def batched_nms(boxes, scores, idxs, iou_threshold):
         _need_cuda(boxes, scores, idxs)
@@ -258,7 +316,7 @@ def register():
 
     for name, fn, fm in (("conv_bn_act", conv_bn_act, conv_bn_act_meta), ("nonlocal_dot", nonlocal_dot, lambda x, *a: torch.empty_like(x)),
                          ("yolox_decode", yolox_decode, yolox_decode_meta), ("nms", nms, nms_meta),
-                         ("soft_nms", soft_nms, soft_nms_meta), ("ufp_pack", ufp_pack, ufp_pack_meta),
+                         ("soft_nms", soft_nms, soft_nms_meta), ("ufp_pack", ufp_pack, ufp_pack_meta), ("voc_ap", voc_ap, voc_ap_meta),
                          ("batched_nms", batched_nms, lambda b, s, i, t: b.new_empty((0,), dtype=torch.int64))):
         impl.impl(name, fn)
         cpu.impl(name, no_cpu)

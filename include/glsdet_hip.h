@@ -658,6 +658,47 @@ int glsdet_coco_match(const double* dt_box, const double* dt_area, const int32_t
                       int32_t* dt_match, unsigned char* dt_ignore, int32_t* gt_match, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * VOC-style mAP (an additive export of ABI 17): the score the drone harness reports, get_map of
+ * drone/models/core/utils_map.py:294-813 as called at get_map.py:121-124 -- the matching of :474-512, the curves of
+ * :570-617, voc_ap :99-140 and the nine picked miss rates of log_average_miss_rate :26-62 -- for every class and
+ * n_thr overlap thresholds in one call, all in fp64, no product fused into a sum.
+ *   dt_box [n_dt][4] left, top, right, bottom / score [n_dt]: class-major, inside a class in the reference's rank
+ *       order (float(confidence) descending, stable over sorted-file then line order); cls_off int32 [n_cls+1]
+ *   the n_pairs (class, image) pairs that own at least one detection:
+ *       pair_off int32 [n_pairs+1] into pair_det int32 [n_dt]: the pair's detection indices, ascending (every
+ *       detection belongs to exactly one pair); gt_off int32 [n_pairs+1] into gt_box fp64 [n_gt_boxes][4] /
+ *       gt_difficult u8 [n_gt_boxes]: the pair's ground truths in file order (a pair may have none)
+ *   n_gt int32 [n_cls] non-difficult ground truths of the class; n_img int32 [n_cls] images that hold one
+ *   min_overlap fp64 [n_thr]; fppi_ref fp64 [9]: the host's np.logspace(-2, 0, 9)
+ * Matching: iw = min(right) - max(left) + 1 (ih alike); a ground truth is a candidate iff iw > 0 and ih > 0;
+ *   ov = iw*ih / ((bb area with +1) + (gt area with +1) - iw*ih); ovmax starts at -1 and is replaced on strict >, so
+ *   the first ground truth in file order keeps a tie; difficult ones are candidates.  ovmax >= min_overlap: a difficult
+ *   match is neither tp nor fp and is not marked used, a used match is fp, otherwise tp; no match is fp.
+ * out (device, caller allocated; nothing needs clearing):
+ *   tp, fp   int32 [n_thr][n_dt]  cumulative counts in rank order per class
+ *   rec      fp64  [n_thr][n_dt]  tp / max(n_gt, 1)        prec  fp64 [n_thr][n_dt]  tp / max(fp + tp, 1)
+ *   mpre     fp64  [n_thr][n_dt]  voc_ap's mpre[1 .. n]: the suffix maximum of [prec..., 0]
+ *   cls_out  fp64  [n_thr][n_cls][16] = ap (terms (mrec[i]-mrec[i-1])*mpre[i] over the i where mrec changes, added one
+ *            at a time in ascending i from 0.0), n_tp, score05_idx (last index with score > 0.5, else 0), F1 / recall /
+ *            precision there (F1 = rec*prec*2 / where(prec+rec == 0, 1, prec+rec); zeros for a class without
+ *            detections), mr9[9]: for each fppi_ref[k] the last j of [-1, fp / float(n_img)...] that is <= it, picked
+ *            from [1, 1 - rec...] (the reference hands `rec` to the parameter it calls `precision`, :617; 1 for a class
+ *            without detections, whose lamr the reference sets to 0), and the final fp count.
+ *   ws : glsdet_voc_ap_workspace_bytes(n_gt_boxes, n_thr) bytes (the `used` flags; 0 for a negative size or n_thr < 1),
+ *        contents irrelevant.
+ * Refused on the host: null or misaligned pointers, negative sizes, n_thr < 1, n_pairs > n_dt, a short workspace.  The
+ * offset arrays live on the device and are not read back here: glsdet_amd/eval/voc.py checks on the host that they are
+ * monotone and that pair_det is a permutation before it uploads them; the kernels clamp every offset to its array, so
+ * malformed offsets give wrong numbers and no fault.                                                                    */
+int64_t glsdet_voc_ap_workspace_bytes(int32_t n_gt_boxes, int32_t n_thr);
+int glsdet_voc_ap(const double* dt_box, const double* score, const int32_t* cls_off, int32_t n_dt, int32_t n_cls,
+                  const int32_t* pair_off, const int32_t* pair_det, const int32_t* gt_off, int32_t n_pairs,
+                  const double* gt_box, const unsigned char* gt_difficult, int32_t n_gt_boxes,
+                  const int32_t* n_gt, const int32_t* n_img, const double* min_overlap, int32_t n_thr,
+                  const double* fppi_ref, int32_t* tp, int32_t* fp, double* rec, double* prec, double* mpre,
+                  double* cls_out, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Plan: a recorded sequence of the calls above, replayed without Python in the loop and
  * capturable into one hipGraph (HIP streams + graphs instead of a tracing compiler).
  * Recording: glsdet_plan_begin(plan) makes every following entry-point call on this
