@@ -14,7 +14,7 @@ from typing import Tuple
 # drone/models/base/yolox.py:240-241
 DEPTH = {"nano": 0.33, "tiny": 0.33, "s": 0.33, "m": 0.67, "l": 1.00, "x": 1.33}
 WIDTH = {"nano": 0.25, "tiny": 0.375, "s": 0.50, "m": 0.75, "l": 1.00, "x": 1.25}
-KINDS = ("base", "gl", "cross")
+KINDS = ("base", "gl", "cross", "cross10")
 
 
 class _Table(OrderedDict):
@@ -153,13 +153,16 @@ def state_dict_shapes(kind: str, phi: str, num_classes: int,
         t.plain(b + ".P4_Identity.conv", c[1], c[1], 5)
     t.any_conv(b + ".bu_conv1", c[1], c[1], 3, dw)
     t.csp(b + ".C3_n4", 2 * c[1], c[2], n, dw)
+    if kind == "cross10":                   # new/yolox10.py:236-255: Patch_Conv_NonLocal_new(C, C, channel_scale=1) on dark3 / 4 / 5
+        for i in range(3):
+            gl_fusion_table(t, "%s.Patch_conv_feat%d" % (b, i + 1), c[i], "non_linear")
     if kind == "gl":
         t.patch_conv(b + ".Patch_conv_feat1", c[0], c[1], True)
         t.patch_conv(b + ".Patch_conv_feat2", c[1], c[0], False)
         t.plain(b + ".P5_Identity.conv", c[2], c[2], 3)
     f = int(256 * wid)
     h = "head"
-    if kind == "cross":
+    if kind in ("cross", "cross10"):
         cross_head_table(t, h, num_classes, wid, dw)
         return t
     for name in ("cls_convs", "reg_convs"):

@@ -142,3 +142,10 @@ class LskCrossYoloBody(CrossYoloBody):
     """drone/models/lsk/yolox6.py = lsk/yolox6_lsk.py: the cross-scale head on lsk/darknet_lsk.py's backbone (an
     LSK.Attention block -- 1x1, GELU, LSKblock, 1x1 + shortcut -- after every stage)."""
     attention_backbone = "lsk"
+
+
+class Cross10YoloBody(CrossYoloBody):
+    """drone/models/new/yolox10.py: feat_i + Patch_Conv_NonLocal_new(feat_i) on dark3 / dark4 / dark5 in front of the
+    PAFPN (:236-266), then the cross-scale head.  Its import of `models.decouple.darknet` is missing from the reference
+    checkout; new/darknet.py has the same classes and exposes dark2."""
+    kind = "cross10"

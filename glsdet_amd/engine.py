@@ -754,17 +754,67 @@ class Engine:
                                        ws.data_ptr(), C.byref(out.as_c()), _stream_ptr(self.stream)), "nonlocal")
         return out
 
-    def nonlocal_multi(self, xs: Sequence[TView], tpgs: Sequence[TView], ci: int, wouts, bouts) -> List[TView]:
-        """1..4 independent non-local blocks (in place on each x) in one set of three launches."""
+    def nonlocal_mfma_takes(self, xs: Sequence[TView], tpgs: Sequence[TView], ci: int, outs: Sequence[TView], wouts=(), bouts=()) -> bool:
+        """the preconditions of glsdet_nonlocal_mfma (include/glsdet_hip.h), evaluated without a call"""
         n = len(xs)
-        ws = self.raw(n * xs[0].n * (8 * ci * ci + xs[0].c * ci) * 4)
+        if not 1 <= n <= 4 or len(tpgs) != n or len(outs) != n:
+            return False
+        cx, nimg, dt = xs[0].c, xs[0].n, xs[0].dtype
+        if ci < 32 or ci % 32 or ci > 1280 or cx < 32 or cx % 32 or cx > 1280 or nimg * n > 65535:
+            return False
+        for x, t, o in zip(xs, tpgs, outs):
+            if (x.c, x.n) != (cx, nimg) or (o.n, o.h, o.w, o.c) != (x.n, x.h, x.w, x.c) or (t.n, t.h, t.w) != (x.n, x.h, x.w):
+                return False
+            if t.c < 3 * ci or x.dtype != dt or t.dtype != dt or o.dtype != dt:
+                return False
+            vn = 16 // _ESIZE[dt]
+            for v in (x, t, o):
+                if v.off % vn or v.sn % vn or v.sh % vn or v.sw % vn or v.buf.data_ptr() % 16:
+                    return False
+        return all(w.data_ptr() % 16 == 0 for w in list(wouts) + list(bouts))
+
+    # Where the matrix-core kernels beat the scalar ones beyond the scalar kernels' own run-to-run spread (DESIGN section 5:
+    # tools/nonlocal_variants.py --sweep on an MI355X, batch 8, four quadrants, ci = cx): {width: smallest pixel count of the
+    # largest set from which they won at every measured size}.  They won at every measured point, in both dtypes, so each
+    # entry is the smallest quadrant that was measured; a width between two measured ones takes the larger of its
+    # neighbours' entries, anything outside the measured range keeps the scalar kernels.
+    NONLOCAL_MFMA_FROM = {c: 6 for c in (64, 96, 128, 192, 256, 320, 384, 512, 640, 1024, 1280)}
+
+    def nonlocal_mfma_pays(self, xs: Sequence[TView], ci: int) -> bool:
+        """the measured per-geometry choice behind mfma="auto"; GLSDET_NONLOCAL_MFMA=1 / 0 overrides it (measurements)"""
+        forced = os.environ.get("GLSDET_NONLOCAL_MFMA", "")
+        if forced in ("0", "1"):
+            return forced == "1"
+        t = self.NONLOCAL_MFMA_FROM
+        if xs[0].c != ci or not min(t) <= ci <= max(t):
+            return False
+        need = max(t[max(c for c in t if c <= ci)], t[min(c for c in t if c >= ci)])
+        return max(x.h * x.w for x in xs) >= need
+
+    def nonlocal_multi(self, xs: Sequence[TView], tpgs: Sequence[TView], ci: int, wouts, bouts,
+                       outs: Optional[Sequence[TView]] = None, mfma=False) -> List[TView]:
+        """1..4 independent non-local blocks in one set of three launches, in place on each x unless `outs` is given.
+        mfma=True: on the matrix-core kernels (glsdet_nonlocal_mfma) where they take the problem; "auto": where they take it
+        AND were measured faster for the geometry (nonlocal_mfma_pays); the kernels of glsdet_nonlocal_multi otherwise --
+        the default, so that every caller that does not ask keeps its bits.  A refusal of the entry point launches nothing
+        and leads to the scalar kernels as well: the preconditions live in the library, nonlocal_mfma_takes only spares the
+        call."""
+        n = len(xs)
+        outs = list(xs) if outs is None else list(outs)
         xa = (View * n)(*[x.as_c() for x in xs])
+        oa = (View * n)(*[o.as_c() for o in outs])
         ta = (View * n)(*[t.as_c() for t in tpgs])
         wa = (C.c_void_p * n)(*[w.data_ptr() for w in wouts])
         ba = (C.c_void_p * n)(*[b.data_ptr() for b in bouts])
-        check(self.lib.glsdet_nonlocal_multi(xa, ta, n, ci, wa, ba, ws.data_ptr(), xa, _stream_ptr(self.stream)),
+        if mfma and self.nonlocal_mfma_takes(xs, tpgs, ci, outs, wouts, bouts) and (mfma != "auto" or self.nonlocal_mfma_pays(xs, ci)):
+            nbytes = self.lib.glsdet_nonlocal_mfma_workspace_bytes(xs[0].n, n, ci, xs[0].c)
+            ws = self.raw(nbytes)
+            if self.lib.glsdet_nonlocal_mfma(xa, ta, n, ci, wa, ba, ws.data_ptr(), nbytes, oa, _stream_ptr(self.stream)) == 0:
+                return outs
+        ws = self.raw(n * xs[0].n * (8 * ci * ci + xs[0].c * ci) * 4)
+        check(self.lib.glsdet_nonlocal_multi(xa, ta, n, ci, wa, ba, ws.data_ptr(), oa, _stream_ptr(self.stream)),
               "nonlocal_multi")
-        return list(xs)
+        return outs
 
     # ---- Patch_Conv_NonLocal_adapt_new: device-side quadrant split
     def attn_split(self, att: TView) -> torch.Tensor:

@@ -385,9 +385,11 @@ class NetBuilder:
         self._rec(p + ".conv_out", y)
         return y
 
-    def nonlocal_blocks(self, ps: Sequence[str], xs: Sequence[TView]) -> List[TView]:
-        """Several independent non-local blocks (the four quadrants), each in place on its x: the
-        theta|phi|g projections go out as one grouped launch."""
+    def nonlocal_blocks(self, ps: Sequence[str], xs: Sequence[TView], outs: Optional[Sequence[TView]] = None,
+                        mfma=False) -> List[TView]:
+        """Several independent non-local blocks (the four quadrants), each in place on its x unless `outs` names other
+        destinations: the theta|phi|g projections go out as one grouped launch.  mfma: Engine.nonlocal_multi(mfma=True)."""
+        outs = list(xs) if outs is None else list(outs)
         ci = self.sd[ps[0] + ".theta.weight"].shape[0]
         packs = []
         for p, x in zip(ps, xs):
@@ -408,9 +410,9 @@ class NetBuilder:
             wouts.append(wout)
             bouts.append(bout)
         if len({(x.n, x.c) for x in xs}) == 1 and len(xs) <= 4 and not os.environ.get("GLSDET_NO_GROUP"):
-            ys = self.e.nonlocal_multi(xs, tpgs, ci, wouts, bouts)
+            ys = self.e.nonlocal_multi(xs, tpgs, ci, wouts, bouts, outs=outs, mfma=mfma)
         else:
-            ys = [self.e.nonlocal_(x, tpg, ci, w, b, out=x) for x, tpg, w, b in zip(xs, tpgs, wouts, bouts)]
+            ys = [self.e.nonlocal_(x, tpg, ci, w, b, out=o) for x, tpg, w, b, o in zip(xs, tpgs, wouts, bouts, outs)]
         for p, y in zip(ps, ys):
             self._rec(p + ".conv_out", y)
         return ys
@@ -491,16 +493,23 @@ class NetBuilder:
             return self.plain(p + ".channel_conv", Z, out=out)
         return self.cba(p + ".channel_conv", Z, out=out)
 
-    def patch_conv_nonlocal_new(self, p: str, x: TView, out: Optional[TView] = None) -> TView:
+    def patch_conv_nonlocal_new(self, p: str, x: TView, out: Optional[TView] = None, res: Optional[TView] = None,
+                                mfma=False) -> TView:
         """Patch_Conv_NonLocal_new (new/Non_local_family.py:208-252).  The four quadrant
-        non-local blocks run IN PLACE on windows of x (x is consumed), so the re-stitch is free."""
-        hh, hw = x.h // 2, x.w // 2
-        wins = (("lt", x.window(0, hh, 0, hw)), ("lb", x.window(hh, x.h, 0, hw)),
-                ("rt", x.window(0, hh, hw, x.w)), ("rb", x.window(hh, x.h, hw, x.w)))
-        self.nonlocal_blocks(["%s.feat_patchconv_%s_nonlocal" % (p, nm) for nm, _ in wins], [w for _, w in wins])
+        non-local blocks run IN PLACE on windows of x (x is consumed), so the re-stitch is free.
+        res: added by the channel_conv, act(conv) + res (new/yolox10.py:250-252 adds the block's input).
+        mfma: the blocks run on the matrix-core kernels where those take them.  With `res` or `mfma` they write the windows
+        of a fresh buffer: x stays intact (it can be `res`) and no copy pass is needed."""
+        names = ("lt", "lb", "rt", "rb")
+        wins = lambda v: [v.window(*w) for w in ((0, v.h // 2, 0, v.w // 2), (v.h // 2, v.h, 0, v.w // 2),
+                                                  (0, v.h // 2, v.w // 2, v.w), (v.h // 2, v.h, v.w // 2, v.w))]
+        fresh = mfma or res is not None
+        S = self.e.tensor(x.n, x.h, x.w, x.c, x.dtype) if fresh else x
+        self.nonlocal_blocks(["%s.feat_patchconv_%s_nonlocal" % (p, nm) for nm in names], wins(x),
+                             outs=wins(S) if fresh else None, mfma=mfma)
         if self.has(p + ".channel_conv.weight"):
-            return self.plain(p + ".channel_conv", x, out=out)
-        return self.cba(p + ".channel_conv", x, out=out)
+            return self.plain(p + ".channel_conv", S, out=out, res=res)
+        return self.cba(p + ".channel_conv", S, out=out, res=res)
 
     def patch_conv_nonlocal_adapt_new(self, p: str, x: TView, out: Optional[TView] = None) -> TView:
         """Patch_Conv_NonLocal_adapt_new (new/Non_local_family.py:272-357).  The quadrant split is computed ON the device
@@ -672,10 +681,13 @@ class NetBuilder:
         return y
 
     # ------------------------------------------------------------------ necks
-    def pafpn(self, p: str, img: torch.Tensor, gl: bool, fold_p5: bool = False) -> List[TView]:
+    def pafpn(self, p: str, img: torch.Tensor, gl: bool, fold_p5: bool = False, residual_gl: bool = False) -> List[TView]:
         """YOLOPAFPN (base/yolox.py:170-234) or its GL-fusion variant
         (block/non_local/yolo_patch_nonlocal_plus.py:180-247) when gl=True.  fold_p5: the caller's head is yolox_head,
-        which may take P5_Identity into its stem (stem_of_identity); the third output is then C3_n4's."""
+        which may take P5_Identity into its stem (stem_of_identity); the third output is then C3_n4's.
+        residual_gl (new/yolox10.py:236-266): the neck reads feat_i + Patch_Conv_NonLocal_new(feat_i) in place of dark3 /
+        dark4 / dark5.  The backbone then writes the three maps to buffers of their own and the sums land where feat1 /
+        feat2 live otherwise (the concat slices); the third goes to the tensor lateral_conv0 reads."""
         sd = self.sd
         c3 = self.conv_out_channels(p + ".backbone.dark3.1.conv3")
         c4 = self.conv_out_channels(p + ".backbone.dark4.1.conv3")
@@ -693,9 +705,14 @@ class NetBuilder:
         cat_p3 = e.tensor(n, h3, w3, 2 * c3)                # [up(P4) | feat1]
         cat_n3 = e.tensor(n, h4, w4, (2 + extra) * c3)      # [down(P3) | P4 | (feat2_patch)]
         cat_n4 = e.tensor(n, h5, w5, 2 * c4)                # [down(P4) | P5]
-        f = self.darknet(p + ".backbone", img, {"dark3": cat_p3.channels(c3, 2 * c3),
-                                                 "dark4": cat_p4.channels(c4, 2 * c4)})
+        homes = {"dark3": cat_p3.channels(c3, 2 * c3), "dark4": cat_p4.channels(c4, 2 * c4)}
+        f = self.darknet(p + ".backbone", img, {} if residual_gl else homes)
         feat1, feat2, feat3 = f["dark3"], f["dark4"], f["dark5"]
+        if residual_gl:
+            sums = []
+            for i, (ft, home) in enumerate(((feat1, homes["dark3"]), (feat2, homes["dark4"]), (feat3, None))):
+                sums.append(self.patch_conv_nonlocal_new("%s.Patch_conv_feat%d" % (p, i + 1), ft, out=home, res=ft, mfma="auto"))
+            feat1, feat2, feat3 = sums
         if gl:
             if fold1:
                 for cv in ("conv1", "conv2"):
@@ -806,17 +823,17 @@ class NetBuilder:
 
 
 def build_forward(kind: str, eng: Engine, sd, img: torch.Tensor, trace: Optional[dict] = None, composed: Optional[dict] = None):
-    """Emit the whole raw forward of a `kind` in {'base','gl','cross'} detector for the static input
+    """Emit the whole raw forward of a `kind` in {'base','gl','cross','cross10'} detector for the static input
     tensor `img` (NCHW fp32 on the device).  Returns (list of fp32 level views, num_classes).
     trace: dict filled with a snapshot of every stored tensor (eager emission only; parity tests).  composed: dict filled
     with the host-composed convs' (w, scale, bias); a trace then keeps the composed forms the benchmark runs."""
     b = NetBuilder(eng, sd)
     b.trace, b.composed = trace, composed
-    if kind not in ("base", "gl", "cross"):
+    if kind not in ("base", "gl", "cross", "cross10"):
         raise ValueError("unknown detector kind %r" % kind)
     fold = kind == "gl" and not b.is_depthwise("head.stems.2")
-    feats = b.pafpn("backbone", img, gl=(kind == "gl"), fold_p5=fold)
-    if kind == "cross":
+    feats = b.pafpn("backbone", img, gl=(kind == "gl"), fold_p5=fold, residual_gl=(kind == "cross10"))
+    if kind in ("cross", "cross10"):
         outs = b.cross_scale_head("head", [b.features["dark2"]] + feats)
     else:
         outs = b.yolox_head("head", feats)

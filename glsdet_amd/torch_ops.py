@@ -10,6 +10,7 @@ allocated by the op on the input's device, nothing synchronises.  There is no CP
         y NHWC [N,Ho,Wo,ceil8(cout)];  act: 0 none 1 silu 2 relu 3 lrelu 4 gelu 5 sigmoid (| 0x100 residual first)
         reference: BaseConv drone/models/base/baseConv.py:6-19 (+ Bottleneck add, darknet.py:61-62)
     glsdet::nonlocal_dot(x, tpg, ci, wout, bout) -> y
+    glsdet::nonlocal_dot_mfma(x, tpg, ci, wout, bout) -> y     (the same on the matrix cores: ci, C multiples of 32)
         Non_local_Block without its three projections: drone/models/block/non_local/Identity_Conv.py:157-173
     glsdet::yolox_decode(levels, num_classes, in_h, in_w, mode=0, sigmoid=3) -> pred [N, A, 5+nc]
         decode_outputs, drone/models/core/utils_bbox.py:254-306 (mode 1: mmdet YOLOXHead._bbox_decode); sigmoid: bit 0
@@ -104,6 +105,7 @@ def register():
     lib_def.define("conv_bn_act(Tensor x, Tensor w, Tensor scale, Tensor bias, int cout, int R, int S, int stride, int pad, "
                    "int act, Tensor? res=None, bool out_fp32=False) -> Tensor")
     lib_def.define("nonlocal_dot(Tensor x, Tensor tpg, int ci, Tensor wout, Tensor bout) -> Tensor")
+    lib_def.define("nonlocal_dot_mfma(Tensor x, Tensor tpg, int ci, Tensor wout, Tensor bout) -> Tensor")
     lib_def.define("yolox_decode(Tensor[] levels, int num_classes, int in_h, int in_w, int mode=0, int sigmoid=3) -> Tensor")
     lib_def.define("nms(Tensor pred, int num_classes, int box_mode, float conf_thres, float nms_thres, int max_det) -> "
                    "(Tensor, Tensor, Tensor)")
@@ -159,6 +161,23 @@ def register():
         check(lib.glsdet_nonlocal(C.byref(_nhwc_view(x, "nonlocal_dot.x")), C.byref(_nhwc_view(tpg, "nonlocal_dot.tpg")), ci,
                                   wout.data_ptr(), bout.data_ptr(), ws.data_ptr(), C.byref(_nhwc_view(y, "nonlocal_dot.y")),
                                   _stream(x)), "nonlocal_dot")
+        return y
+
+    def nonlocal_dot_mfma(x, tpg, ci, wout, bout):
+        """nonlocal_dot on the matrix-core kernels (glsdet_nonlocal_mfma: ci and C multiples of 32, at most 1280); a shape
+        they do not take is an error here, not a switch to the other kernels"""
+        lib = _lib.load()
+        _need_cuda(x, tpg, wout, bout)
+        if wout.dtype != torch.float32 or bout.dtype != torch.float32 or not wout.is_contiguous() or \
+                tuple(wout.shape) != (x.shape[3], ci) or bout.numel() != x.shape[3] or tpg.shape[3] < 3 * ci:
+            raise RuntimeError("nonlocal_dot_mfma: wout fp32 [C, ci], bout fp32 [C], tpg NHWC with >= 3*ci channels")
+        y = torch.empty_like(x)
+        nbytes = lib.glsdet_nonlocal_mfma_workspace_bytes(x.shape[0], 1, ci, x.shape[3])
+        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=x.device)
+        xa, ta, ya = (View * 1)(_nhwc_view(x, "nonlocal_dot_mfma.x")), (View * 1)(_nhwc_view(tpg, "nonlocal_dot_mfma.tpg")), \
+            (View * 1)(_nhwc_view(y, "nonlocal_dot_mfma.y"))
+        wa, ba = (C.c_void_p * 1)(wout.data_ptr()), (C.c_void_p * 1)(bout.data_ptr())
+        check(lib.glsdet_nonlocal_mfma(xa, ta, 1, ci, wa, ba, ws.data_ptr(), nbytes, ya, _stream(x)), "nonlocal_dot_mfma")
         return y
 
     # ------------------------------------------------------------------ yolox_decode
@@ -315,6 +334,7 @@ def register():
         return torch.argmax(same.to(torch.int8), dim=1)          # first (lowest) index of the identical row
 
     for name, fn, fm in (("conv_bn_act", conv_bn_act, conv_bn_act_meta), ("nonlocal_dot", nonlocal_dot, lambda x, *a: torch.empty_like(x)),
+                         ("nonlocal_dot_mfma", nonlocal_dot_mfma, lambda x, *a: torch.empty_like(x)),
                          ("yolox_decode", yolox_decode, yolox_decode_meta), ("nms", nms, nms_meta),
                          ("soft_nms", soft_nms, soft_nms_meta), ("ufp_pack", ufp_pack, ufp_pack_meta), ("voc_ap", voc_ap, voc_ap_meta),
                          ("batched_nms", batched_nms, lambda b, s, i, t: b.new_empty((0,), dtype=torch.int64))):

@@ -268,6 +268,20 @@ int glsdet_nonlocal(const glsdet_view* x, const glsdet_view* tpg, int32_t ci,
 int glsdet_nonlocal_multi(const glsdet_view* x, const glsdet_view* tpg, int32_t n_sets, int32_t ci,
                           const float* const* wout, const float* const* bout, float* gram,
                           const glsdet_view* out, void* stream);
+/* The same 1..4 blocks on the matrix cores (additive exports of ABI 17), for the wide blocks of new/yolox10.py:236-266:
+ * Patch_Conv_NonLocal_new on dark3 / dark4 / dark5 with inter_channels = C (Non_local_family.py:32-48), i.e. ci = cx =
+ * 128 .. 1280 at the input resolution.  Semantics, association (Gram per pixel slice with the slicing rule of
+ * glsdet_nonlocal_multi, a fold that adds the slices in a fixed order, apply), workspace layout and determinism are those
+ * of glsdet_nonlocal_multi; no rounding is added (theta / phi / g in the storage type, G, P, wout, bout fp32; the fp16 Gram
+ * on v_mfma_f32_32x32x16_f16, everything else on v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain): only the order of the
+ * sums differs.  out[q] may equal x[q].  Refused (negative code, nothing launched) unless: n_sets in 1..4; the sets agree
+ * in n and channels; ci and x.c multiples of 32, at most 1280; tpg.c >= 3 ci; every base and stride (a window's offset is
+ * part of its base), wout[q] and bout[q] multiples of 16 bytes; one dtype (f16 / f32) for x, tpg and out; ws 256-byte
+ * aligned with ws_bytes >= glsdet_nonlocal_mfma_workspace_bytes(n, n_sets, ci, x.c) (0 for arguments out of range).  */
+int64_t glsdet_nonlocal_mfma_workspace_bytes(int32_t n, int32_t n_sets, int32_t ci, int32_t cx);
+int glsdet_nonlocal_mfma(const glsdet_view* x, const glsdet_view* tpg, int32_t n_sets, int32_t ci,
+                         const float* const* wout, const float* const* bout, void* ws, int64_t ws_bytes,
+                         const glsdet_view* out, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Patch_Conv_NonLocal_adapt_new: the data-dependent quadrant split (drone/models/new/Non_local_family.py:272-357)
