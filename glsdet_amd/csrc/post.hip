@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void nms_filter_kernel(const float* __restrict
 // (score desc, anchor asc) order.  Exact and deterministic.  Workgroup = 64 candidates x 4
 // slices of the comparison range; tiles of 256 (score, anchor) pairs go through LDS and each
 // thread scans its quarter of the tile (broadcast reads), partial ranks are summed in LDS.
-__global__ __launch_bounds__(256) void nms_rank_kernel(int max_cand, NmsWs ws, int fused = 0) {
+__global__ __launch_bounds__(256) void nms_rank_kernel(int max_cand, NmsWs ws, int fused) {
   __shared__ float s_score[256];
   __shared__ int s_anchor[256];
   __shared__ int s_part[256];
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void nms_rank_kernel(int max_cand, NmsWs ws, i
 // Stored column-block major so that the scan reads 64 consecutive rows of one column block
 // as one coalesced 512-byte wave load.  The grid is fixed; each 64-thread block walks the
 // (row block, column block) pairs of the ACTUAL candidate count (known only on the device).
-__global__ __launch_bounds__(64) void nms_mask_kernel(int max_cand, int nw, float thr, NmsWs ws, float one = 0.f, int fused = 0) {
+__global__ __launch_bounds__(64) void nms_mask_kernel(int max_cand, int nw, float thr, NmsWs ws, float one, int fused) {
   const int b = blockIdx.y;
   if (fused && ws.cnt[gridDim.y + b]) return;
   const int n = min(ws.cnt[b], max_cand);
@@ -249,7 +249,7 @@ __device__ __forceinline__ unsigned long long wave_or(unsigned long long v) {
 // A sweep that changes nothing proves the fixed point.  One 1024-thread workgroup / image.
 #define GLS_NMS_MAXW 512    // 512 * 64 = 32768 candidates max
 __global__ __launch_bounds__(1024) void nms_scan_kernel(int max_cand, int nw, int max_det, NmsWs ws, float* dets,
-                                                        int* count, int fused = 0) {
+                                                        int* count, int fused) {
   __shared__ unsigned long long s_keep[GLS_NMS_MAXW];
   __shared__ int s_prefix[GLS_NMS_MAXW];
   __shared__ int s_changed;
@@ -982,6 +982,90 @@ static long nms_layout(int n, int max_cand, NmsWs* ws, char* base, bool with_mas
   return off;
 }
 
+// ---------------------------------------------------------------------------- host helpers of the entry points
+// The workspace contract of every entry point that works on an NmsWs: a 256-byte aligned base, the layout of nms_layout
+// behind the `off` bytes another part of the same workspace takes (gfl_detect's per-level part), and room for all of it.
+static int nms_workspace(const char* who, int n, int max_cand, bool with_mask, void* wsp, int64_t ws_bytes, NmsWs* ws,
+                         long off = 0) {
+  if ((uintptr_t)wsp & 255) GLS_FAIL(GLSDET_E_ALIGN, "%s: workspace must be 256-byte aligned", who);
+  const long need = off + nms_layout(n, max_cand, ws, (char*)wsp + off, with_mask);
+  if (ws_bytes < need) GLS_FAIL(GLSDET_E_CAPACITY, "%s: workspace %ld < %ld bytes", who, (long)ws_bytes, need);
+  return 0;
+}
+
+// Greedy NMS of the candidates each of the n_img images has in ws (cbox / cext / canchor / cscore, count in ws.cnt):
+// rank (score order) -> mask (same class and IoU > thr; one = 1: the '+1' pixel-area convention) -> scan (keep /
+// suppress; the first max_det kept rows go to dets, the counts to count).  fused: skip the images whose flag in
+// ws.cnt[n_img ..] says that the class-segmented kernels finished them.
+static void launch_greedy_nms(hipStream_t st, int n_img, int max_cand, float thr, float one, int max_det, const NmsWs& ws,
+                              float* dets, int* count, int fused) {
+  const int nw = (max_cand + 63) / 64;       // 64-bit words of a mask row
+  // rank: one workgroup per 64 candidates of an image
+  hipLaunchKernelGGL(nms_rank_kernel, dim3((max_cand + 63) / 64, n_img), dim3(256), 0, st, max_cand, ws, fused);
+  // mask: a fixed grid, the candidate count is known only on the device: 2048 one-wave blocks per image walk its block pairs
+  hipLaunchKernelGGL(nms_mask_kernel, dim3(2048, n_img), dim3(64), 0, st, max_cand, nw, thr, ws, one, fused);
+  // scan: one 1024-thread workgroup per image, the keep bits of the fixed point live in its LDS
+  hipLaunchKernelGGL(nms_scan_kernel, dim3(n_img), dim3(1024), 0, st, max_cand, nw, max_det, ws, dets, count, fused);
+}
+
+// a post-processing op of a plan: no MFMA work, `bytes` of HBM traffic
+static OpRecord post_op(const char* name, double bytes) {
+  OpRecord op;
+  op.kind = 6, op.flops = 0, op.bytes = bytes, op.name = name;
+  return op;
+}
+
+// The front that glsdet_gfl_detect and glsdet_gfl_candidates (`who`, for the messages) share: the checks of the sizes and
+// of the level views, the views as kernel arguments, the op's HBM bytes (every logit read once), and the launches up to
+// the per-level top-k.  max_cand2: gfl_detect's merged candidate count (0: none); cand: gfl_candidates' export rows (null: none).
+struct GflFront {
+  GflArgs a;
+  int maxhw;            // pixels of the largest level
+  double bytes;
+
+  int fill(const char* who, const glsdet_view* cls, const glsdet_view* reg, int n_levels, const int32_t* strides,
+           int num_classes, int reg_max, int in_h, int in_w, const float* img_hw, float score_thr, int nms_pre, int max_cand,
+           int max_det, int max_cand2, const void* wsp, const void* cand) {
+    if (n_levels < 1 || n_levels > GLS_MAX_LEVELS || num_classes < 1 || reg_max < 1 || reg_max > 63 || nms_pre < 1 ||
+        max_cand < 1 || max_det < 1)
+      GLS_FAIL(GLSDET_E_ARG, "%s: bad sizes", who);
+    if (max_cand > GLS_NMS_MAXW * 64 || max_cand2 > GLS_NMS_MAXW * 64)
+      GLS_FAIL(GLSDET_E_ARG, "%s: max_cand%s above %d", who, max_cand2 ? " / n_levels*nms_pre" : "", GLS_NMS_MAXW * 64);
+    if (((uintptr_t)wsp & 255) || ((uintptr_t)cand & 15))
+      GLS_FAIL(GLSDET_E_ALIGN, "%s: workspace must be 256-byte%s aligned", who, cand ? " and cand 16-byte" : "");
+    const std::string cls_name = std::string(who) + ".cls", reg_name = std::string(who) + ".reg";
+    a = {};
+    maxhw = 0;
+    bytes = 0;
+    for (int l = 0; l < n_levels; ++l) {
+      int rc;
+      if ((rc = check_view(cls[l], cls_name.c_str(), false))) return rc;
+      if ((rc = check_view(reg[l], reg_name.c_str(), false))) return rc;
+      if (cls[l].dtype != GLSDET_F32 || reg[l].dtype != GLSDET_F32) GLS_FAIL(GLSDET_E_ARG, "%s: levels must be fp32", who);
+      if (cls[l].c < num_classes || reg[l].c < 4 * (reg_max + 1) || cls[l].n != cls[0].n || reg[l].n != cls[0].n ||
+          reg[l].h != cls[l].h || reg[l].w != cls[l].w || strides[l] < 1)
+        GLS_FAIL(GLSDET_E_ARG, "%s: level %d extent mismatch", who, l);
+      a.cls[l] = (const float*)cls[l].base; a.reg[l] = (const float*)reg[l].base;
+      a.csn[l] = cls[l].sn; a.csh[l] = cls[l].sh; a.csw[l] = cls[l].sw;
+      a.rsn[l] = reg[l].sn; a.rsh[l] = reg[l].sh; a.rsw[l] = reg[l].sw;
+      a.H[l] = cls[l].h; a.W[l] = cls[l].w;
+      a.stride[l] = (float)strides[l];
+      if (cls[l].h * cls[l].w > maxhw) maxhw = cls[l].h * cls[l].w;
+      bytes += (double)cls[0].n * a.H[l] * a.W[l] * (num_classes + 4.0 * (reg_max + 1)) * 4.0;
+    }
+    a.n_levels = n_levels; a.nc = num_classes; a.reg_max = reg_max; a.n = cls[0].n;
+    a.in_h = (float)in_h; a.in_w = (float)in_w; a.thr = score_thr; a.img_hw = img_hw;
+    return 0;
+  }
+
+  // candidates above the threshold per (image, level) into w1, then their score order (the top-k is a prefix of it)
+  void launch(hipStream_t st, int max_cand, const NmsWs& w1, int* status) const {
+    hipLaunchKernelGGL(reset_counters_kernel, dim3(1), dim3(256), 0, st, w1.cnt, a.n * a.n_levels, status);
+    hipLaunchKernelGGL(gfl_filter_kernel, dim3((maxhw + 255) / 256, a.n, a.n_levels), dim3(256), 0, st, a, max_cand, w1, status);
+    hipLaunchKernelGGL(nms_rank_kernel, dim3((max_cand + 63) / 64, a.n * a.n_levels), dim3(256), 0, st, max_cand, w1, 0);
+  }
+};
+
 }  // namespace glsdet
 
 using namespace glsdet;
@@ -1051,18 +1135,14 @@ extern "C" int glsdet_nms(const float* pred, int32_t n, int32_t A, int32_t num_c
   if (!pred || !dets || !count || !status || !wsp) GLS_FAIL(GLSDET_E_ARG, "nms: null argument");
   if (n < 1 || A < 1 || num_classes < 1 || max_cand < 1 || max_det < 1) GLS_FAIL(GLSDET_E_ARG, "nms: bad sizes");
   if (max_cand > GLS_NMS_MAXW * 64) GLS_FAIL(GLSDET_E_ARG, "nms: max_cand %d > %d", max_cand, GLS_NMS_MAXW * 64);
-  if ((uintptr_t)wsp & 255) GLS_FAIL(GLSDET_E_ALIGN, "nms: workspace must be 256-byte aligned");
   NmsWs ws;
-  const long need = nms_layout(n, max_cand, &ws, (char*)wsp);
-  if (ws_bytes < need) GLS_FAIL(GLSDET_E_CAPACITY, "nms: workspace %ld < %ld bytes", (long)ws_bytes, need);
+  int rc;
+  if ((rc = nms_workspace("nms", n, max_cand, true, wsp, ws_bytes, &ws))) return rc;
   const int nw = (max_cand + 63) / 64;
-  OpRecord op;
-  op.kind = 6;
-  op.flops = 0;
-  op.bytes = (double)n * A * (5 + num_classes) * 4.0;
   static const bool no_fused = getenv("GLSDET_NO_FUSED_NMS") != nullptr;       // A/B switch: the three-kernel path of rounds 1-2
   const int key_ok = (A < (1 << 24) && num_classes <= 255) ? 1 : 0;           // bit fields of the fused kernel's sort key
-  op.name = no_fused ? "nms(filter+rank+mask+scan)" : "nms(filter + class sort + same-class mask + blocked scan)";
+  OpRecord op = post_op(no_fused ? "nms(filter+rank+mask+scan)" : "nms(filter + class sort + same-class mask + blocked scan)",
+                        (double)n * A * (5 + num_classes) * 4.0);
   op.launch = [=](hipStream_t st) -> int {
     hipLaunchKernelGGL(reset_counters_kernel, dim3(1), dim3(256), 0, st, ws.cnt, 2 * n, status);
     long g = ((long)n * A + 255) / 256;
@@ -1077,41 +1157,12 @@ extern "C" int glsdet_nms(const float* pred, int32_t n, int32_t A, int32_t num_c
       hipLaunchKernelGGL(nms_cscan_kernel, dim3(n), dim3(1024), 0, st, max_cand, nw, max_det, ws, dets, count, dbg);
       fused = 1;
     }
-    if (!fused || max_cand > GLS_NMSF_MAX || !key_ok) {      // images the fused kernel cannot take (its flags decide per image)
-      hipLaunchKernelGGL(nms_rank_kernel, dim3((max_cand + 63) / 64, n), dim3(256), 0, st, max_cand, ws, fused);
-      hipLaunchKernelGGL(nms_mask_kernel, dim3(2048, n), dim3(64), 0, st, max_cand, nw, nms_thres, ws, 0.f, fused);
-      hipLaunchKernelGGL(nms_scan_kernel, dim3(n), dim3(1024), 0, st, max_cand, nw, max_det, ws, dets, count, fused);
-    }
+    if (!fused || max_cand > GLS_NMSF_MAX || !key_ok)        // images the fused kernel cannot take (its flags decide per image)
+      launch_greedy_nms(st, n, max_cand, nms_thres, 0.f, max_det, ws, dets, count, fused);
     GLS_HIP(hipGetLastError());
     return 0;
   };
   return submit(std::move(op), stream);
-}
-
-// the level views of glsdet_gfl_detect / glsdet_gfl_candidates -> kernel arguments (who = the entry point, for the messages)
-static int gfl_fill_args(const glsdet_view* cls, const glsdet_view* reg, int n_levels, const int32_t* strides, int num_classes,
-                         int reg_max, int in_h, int in_w, const float* img_hw, float score_thr, const char* who,
-                         const char* cls_name, const char* reg_name, GflArgs& a, int& maxhw) {
-  a = {};
-  maxhw = 0;
-  for (int l = 0; l < n_levels; ++l) {
-    int rc;
-    if ((rc = check_view(cls[l], cls_name, false))) return rc;
-    if ((rc = check_view(reg[l], reg_name, false))) return rc;
-    if (cls[l].dtype != GLSDET_F32 || reg[l].dtype != GLSDET_F32) GLS_FAIL(GLSDET_E_ARG, "%s: levels must be fp32", who);
-    if (cls[l].c < num_classes || reg[l].c < 4 * (reg_max + 1) || cls[l].n != cls[0].n || reg[l].n != cls[0].n ||
-        reg[l].h != cls[l].h || reg[l].w != cls[l].w || strides[l] < 1)
-      GLS_FAIL(GLSDET_E_ARG, "%s: level %d extent mismatch", who, l);
-    a.cls[l] = (const float*)cls[l].base; a.reg[l] = (const float*)reg[l].base;
-    a.csn[l] = cls[l].sn; a.csh[l] = cls[l].sh; a.csw[l] = cls[l].sw;
-    a.rsn[l] = reg[l].sn; a.rsh[l] = reg[l].sh; a.rsw[l] = reg[l].sw;
-    a.H[l] = cls[l].h; a.W[l] = cls[l].w;
-    a.stride[l] = (float)strides[l];
-    if (cls[l].h * cls[l].w > maxhw) maxhw = cls[l].h * cls[l].w;
-  }
-  a.n_levels = n_levels; a.nc = num_classes; a.reg_max = reg_max; a.n = cls[0].n;
-  a.in_h = (float)in_h; a.in_w = (float)in_w; a.thr = score_thr; a.img_hw = img_hw;
-  return 0;
 }
 
 extern "C" int64_t glsdet_gfl_workspace_bytes(int32_t n, int32_t n_levels, int32_t max_cand, int32_t nms_pre) {
@@ -1126,41 +1177,22 @@ extern "C" int glsdet_gfl_detect(const glsdet_view* cls, const glsdet_view* reg,
                                  int32_t nms_pre, float iou_thr, int32_t max_cand, int32_t max_det, float* dets,
                                  int32_t* count, int32_t* status, void* wsp, int64_t ws_bytes, void* stream) {
   if (!cls || !reg || !strides || !dets || !count || !status || !wsp) GLS_FAIL(GLSDET_E_ARG, "gfl_detect: null argument");
-  if (n_levels < 1 || n_levels > GLS_MAX_LEVELS || num_classes < 1 || reg_max < 1 || reg_max > 63 || nms_pre < 1 ||
-      max_cand < 1 || max_det < 1)
-    GLS_FAIL(GLSDET_E_ARG, "gfl_detect: bad sizes");
   const int max_cand2 = n_levels * nms_pre;
-  if (max_cand > GLS_NMS_MAXW * 64 || max_cand2 > GLS_NMS_MAXW * 64)
-    GLS_FAIL(GLSDET_E_ARG, "gfl_detect: max_cand / n_levels*nms_pre above %d", GLS_NMS_MAXW * 64);
-  if ((uintptr_t)wsp & 255) GLS_FAIL(GLSDET_E_ALIGN, "gfl_detect: workspace must be 256-byte aligned");
-  GflArgs a;
-  int maxhw, rc;
-  if ((rc = gfl_fill_args(cls, reg, n_levels, strides, num_classes, reg_max, in_h, in_w, img_hw, score_thr, "gfl_detect",
-                          "gfl_detect.cls", "gfl_detect.reg", a, maxhw)))
+  GflFront f;
+  int rc;
+  if ((rc = f.fill("gfl_detect", cls, reg, n_levels, strides, num_classes, reg_max, in_h, in_w, img_hw, score_thr, nms_pre,
+                   max_cand, max_det, max_cand2, wsp, nullptr)))
     return rc;
-  const int n = a.n;
-  NmsWs w1, w2;
-  const long need1 = nms_layout(n * n_levels, max_cand, &w1, (char*)wsp, false);
-  const long off2 = align_up(need1, 256);
-  const long need = off2 + nms_layout(n, max_cand2, &w2, (char*)wsp + off2, true);
-  if (ws_bytes < need) GLS_FAIL(GLSDET_E_CAPACITY, "gfl_detect: workspace %ld < %ld bytes", (long)ws_bytes, need);
-  const int nw2 = (max_cand2 + 63) / 64;
-  double bytes = 0;
-  for (int l = 0; l < n_levels; ++l) bytes += (double)n * a.H[l] * a.W[l] * (num_classes + 4.0 * (reg_max + 1)) * 4.0;
-  OpRecord op;
-  op.kind = 6;
-  op.flops = 0;
-  op.bytes = bytes;
-  op.name = "gfl_detect(filter+topk+merge+nms)";
+  const int n = f.a.n;
+  NmsWs w1, w2;      // the per-level candidates (no mask), then behind them the merged ones of the NMS
+  const long off2 = nms_layout(n * n_levels, max_cand, &w1, (char*)wsp, false);
+  if ((rc = nms_workspace("gfl_detect", n, max_cand2, true, wsp, ws_bytes, &w2, off2))) return rc;
+  OpRecord op = post_op("gfl_detect(filter+topk+merge+nms)", f.bytes);
   op.launch = [=](hipStream_t st) -> int {
-    hipLaunchKernelGGL(reset_counters_kernel, dim3(1), dim3(256), 0, st, w1.cnt, n * n_levels, status);
-    hipLaunchKernelGGL(gfl_filter_kernel, dim3((maxhw + 255) / 256, n, n_levels), dim3(256), 0, st, a, max_cand, w1, status);
-    hipLaunchKernelGGL(nms_rank_kernel, dim3((max_cand + 63) / 64, n * n_levels), dim3(256), 0, st, max_cand, w1);
+    f.launch(st, max_cand, w1, status);
     hipLaunchKernelGGL(gfl_merge_kernel, dim3((max_cand2 + 255) / 256, n), dim3(256), 0, st, n_levels, max_cand, nms_pre,
                        max_cand2, w1, w2, scale_factors);
-    hipLaunchKernelGGL(nms_rank_kernel, dim3((max_cand2 + 63) / 64, n), dim3(256), 0, st, max_cand2, w2);
-    hipLaunchKernelGGL(nms_mask_kernel, dim3(2048, n), dim3(64), 0, st, max_cand2, nw2, iou_thr, w2);
-    hipLaunchKernelGGL(nms_scan_kernel, dim3(n), dim3(1024), 0, st, max_cand2, nw2, max_det, w2, dets, count);
+    launch_greedy_nms(st, n, max_cand2, iou_thr, 0.f, max_det, w2, dets, count, 0);
     GLS_HIP(hipGetLastError());
     return 0;
   };
@@ -1179,36 +1211,21 @@ extern "C" int glsdet_gfl_candidates(const glsdet_view* cls, const glsdet_view* 
                                      void* wsp, int64_t ws_bytes, void* stream) {
   if (!cls || !reg || !strides || !cand || !cand_count || !status || !wsp)
     GLS_FAIL(GLSDET_E_ARG, "gfl_candidates: null argument");
-  if (n_levels < 1 || n_levels > GLS_MAX_LEVELS || num_classes < 1 || reg_max < 1 || reg_max > 63 || nms_pre < 1 ||
-      max_cand < 1)
-    GLS_FAIL(GLSDET_E_ARG, "gfl_candidates: bad sizes");
-  if (max_cand > GLS_NMS_MAXW * 64) GLS_FAIL(GLSDET_E_ARG, "gfl_candidates: max_cand above %d", GLS_NMS_MAXW * 64);
-  if (((uintptr_t)wsp & 255) || ((uintptr_t)cand & 15))
-    GLS_FAIL(GLSDET_E_ALIGN, "gfl_candidates: workspace must be 256-byte and cand 16-byte aligned");
-  GflArgs a;
-  int maxhw, rc;
-  if ((rc = gfl_fill_args(cls, reg, n_levels, strides, num_classes, reg_max, in_h, in_w, img_hw, score_thr,
-                          "gfl_candidates", "gfl_candidates.cls", "gfl_candidates.reg", a, maxhw)))
+  GflFront f;
+  int rc;
+  if ((rc = f.fill("gfl_candidates", cls, reg, n_levels, strides, num_classes, reg_max, in_h, in_w, img_hw, score_thr, nms_pre,
+                   max_cand, 1, 0, wsp, cand)))
     return rc;
-  const int n = a.n;
+  const int n = f.a.n;
   long need_cap = 0;
-  for (int l = 0; l < n_levels; ++l) need_cap += std::min((long)nms_pre, (long)a.H[l] * a.W[l] * num_classes);
+  for (int l = 0; l < n_levels; ++l) need_cap += std::min((long)nms_pre, (long)f.a.H[l] * f.a.W[l] * num_classes);
   if (cap < need_cap)
     GLS_FAIL(GLSDET_E_CAPACITY, "gfl_candidates: cap %d < sum over levels of min(nms_pre, H*W*nc) = %ld", cap, need_cap);
   NmsWs w1;
-  const long need = nms_layout(n * n_levels, max_cand, &w1, (char*)wsp, false);
-  if (ws_bytes < need) GLS_FAIL(GLSDET_E_CAPACITY, "gfl_candidates: workspace %ld < %ld bytes", (long)ws_bytes, need);
-  double bytes = 0;
-  for (int l = 0; l < n_levels; ++l) bytes += (double)n * a.H[l] * a.W[l] * (num_classes + 4.0 * (reg_max + 1)) * 4.0;
-  OpRecord op;
-  op.kind = 6;
-  op.flops = 0;
-  op.bytes = bytes;
-  op.name = "gfl_candidates(filter+topk+export)";
+  if ((rc = nms_workspace("gfl_candidates", n * n_levels, max_cand, false, wsp, ws_bytes, &w1))) return rc;
+  OpRecord op = post_op("gfl_candidates(filter+topk+export)", f.bytes);
   op.launch = [=](hipStream_t st) -> int {
-    hipLaunchKernelGGL(reset_counters_kernel, dim3(1), dim3(256), 0, st, w1.cnt, n * n_levels, status);
-    hipLaunchKernelGGL(gfl_filter_kernel, dim3((maxhw + 255) / 256, n, n_levels), dim3(256), 0, st, a, max_cand, w1, status);
-    hipLaunchKernelGGL(nms_rank_kernel, dim3((max_cand + 63) / 64, n * n_levels), dim3(256), 0, st, max_cand, w1);
+    f.launch(st, max_cand, w1, status);
     hipLaunchKernelGGL(gfl_export_kernel, dim3((cap + 255) / 256, n), dim3(256), 0, st, n_levels, max_cand, nms_pre, w1,
                        (float4*)cand, cap, cand_count);
     GLS_HIP(hipGetLastError());
@@ -1251,24 +1268,16 @@ extern "C" int glsdet_aug_merge_nms(const float* const* cands, const int32_t* co
   if (total > GLS_NMS_MAXW * 64)
     GLS_FAIL(GLSDET_E_ARG, "aug_merge_nms: the candidate capacities sum to %ld, above the NMS limit of %d; lower nms_pre", total,
              GLS_NMS_MAXW * 64);
-  if ((uintptr_t)wsp & 255) GLS_FAIL(GLSDET_E_ALIGN, "aug_merge_nms: workspace must be 256-byte aligned");
   a.K = n_augs; a.n = n; a.meta = aug_meta;
   const int max_cand = (int)total;
   NmsWs w;
-  const long need = nms_layout(n, max_cand, &w, (char*)wsp, true);
-  if (ws_bytes < need) GLS_FAIL(GLSDET_E_CAPACITY, "aug_merge_nms: workspace %ld < %ld bytes", (long)ws_bytes, need);
-  const int nw = (max_cand + 63) / 64;
-  OpRecord op;
-  op.kind = 6;
-  op.flops = 0;
-  op.bytes = (double)n * max_cand * 64.0;
-  op.name = "aug_merge_nms(map back+concat+nms)";
+  int rc;
+  if ((rc = nms_workspace("aug_merge_nms", n, max_cand, true, wsp, ws_bytes, &w))) return rc;
+  OpRecord op = post_op("aug_merge_nms(map back+concat+nms)", (double)n * max_cand * 64.0);
   op.launch = [=](hipStream_t st) -> int {
     hipLaunchKernelGGL(reset_counters_kernel, dim3(1), dim3(256), 0, st, w.cnt, 2 * n, status);
     hipLaunchKernelGGL(aug_mapback_kernel, dim3((max_cand + 255) / 256, n), dim3(256), 0, st, a, max_cand, w);
-    hipLaunchKernelGGL(nms_rank_kernel, dim3((max_cand + 63) / 64, n), dim3(256), 0, st, max_cand, w);
-    hipLaunchKernelGGL(nms_mask_kernel, dim3(2048, n), dim3(64), 0, st, max_cand, nw, iou_thr, w);
-    hipLaunchKernelGGL(nms_scan_kernel, dim3(n), dim3(1024), 0, st, max_cand, nw, max_det, w, dets, count);
+    launch_greedy_nms(st, n, max_cand, iou_thr, 0.f, max_det, w, dets, count, 0);
     if (out_scale)
       hipLaunchKernelGGL(aug_scale_kernel, dim3((max_det + 255) / 256, n), dim3(256), 0, st, dets, count, max_det, out_scale);
     GLS_HIP(hipGetLastError());
@@ -1305,11 +1314,7 @@ extern "C" int glsdet_pack_detections(const float* dets, const int32_t* count, i
                                       float* out, void* stream) {
   if (!dets || !count || !out) GLS_FAIL(GLSDET_E_ARG, "pack_detections: null argument");
   if (n < 1 || max_det < 1 || cap < 1) GLS_FAIL(GLSDET_E_ARG, "pack_detections: bad sizes");
-  OpRecord op;
-  op.kind = 6;
-  op.flops = 0;
-  op.bytes = 2.0 * n * (cap + 1) * 28.0;
-  op.name = "pack_detections";
+  OpRecord op = post_op("pack_detections", 2.0 * n * (cap + 1) * 28.0);
   op.launch = [=](hipStream_t st) -> int {
     long g = ((long)n * (cap + 1) * 7 + 255) / 256;
     if (g > 2048) g = 2048;
@@ -1333,16 +1338,10 @@ extern "C" int glsdet_ufp_backmap_merge(const float* dets, const int32_t* count,
     GLS_FAIL(GLSDET_E_ARG, "ufp_backmap_merge: null argument");
   if (max_det < 1 || n_chips < 0 || max_cand < 1 || max_out < 1 || max_cand > GLS_NMS_MAXW * 64)
     GLS_FAIL(GLSDET_E_ARG, "ufp_backmap_merge: bad sizes");
-  if ((uintptr_t)wsp & 255) GLS_FAIL(GLSDET_E_ALIGN, "ufp_backmap_merge: workspace must be 256-byte aligned");
   NmsWs ws;
-  const long need = nms_layout(1, max_cand, &ws, (char*)wsp, true);
-  if (ws_bytes < need) GLS_FAIL(GLSDET_E_CAPACITY, "ufp_backmap_merge: workspace %ld < %ld bytes", (long)ws_bytes, need);
-  const int nw = (max_cand + 63) / 64;
-  OpRecord op;
-  op.kind = 6;
-  op.flops = 0;
-  op.bytes = 28.0 * max_det * (n_chips > 0 ? n_chips : 1);
-  op.name = "ufp_backmap+merge_nms";
+  int rc;
+  if ((rc = nms_workspace("ufp_backmap_merge", 1, max_cand, true, wsp, ws_bytes, &ws))) return rc;
+  OpRecord op = post_op("ufp_backmap+merge_nms", 28.0 * max_det * (n_chips > 0 ? n_chips : 1));
   op.launch = [=](hipStream_t st) -> int {
     hipLaunchKernelGGL(reset_counters_kernel, dim3(1), dim3(256), 0, st, ws.cnt, 1, status);
     if (n_chips > 0) {
@@ -1351,9 +1350,7 @@ extern "C" int glsdet_ufp_backmap_merge(const float* dets, const int32_t* count,
       hipLaunchKernelGGL(ufp_backmap_kernel, dim3((unsigned)g), dim3(256), 0, st, dets, count, max_det, chips, n_chips, iof_thr,
                          max_cand, ws, status);
     }
-    hipLaunchKernelGGL(nms_rank_kernel, dim3((max_cand + 63) / 64, 1), dim3(256), 0, st, max_cand, ws);
-    hipLaunchKernelGGL(nms_mask_kernel, dim3(2048, 1), dim3(64), 0, st, max_cand, nw, nms_thr, ws, 1.0f);
-    hipLaunchKernelGGL(nms_scan_kernel, dim3(1), dim3(1024), 0, st, max_cand, nw, max_out, ws, out, out_count);
+    launch_greedy_nms(st, 1, max_cand, nms_thr, 1.0f, max_out, ws, out, out_count, 0);
     GLS_HIP(hipGetLastError());
     return 0;
   };

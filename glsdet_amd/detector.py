@@ -2,22 +2,21 @@
 (optionally one hipGraph) per input shape, no Python in the per-layer loop."""
 from __future__ import annotations
 
-import threading
-from typing import Dict, List, Optional, Tuple
+from typing import List, Optional
 
 import numpy as np
 import torch
 
-from . import _lib
-from .engine import DECODE_MODES, Engine, Plan, TView
+from .engine import DECODE_MODES, Engine
 from .nets import build_forward
+from .plans import PlanBacked
 
 
 class _Compiled:
     __slots__ = ("img", "plan", "levels", "stems", "decoded", "nmsb", "eng", "post", "graph_stream", "scale")
 
 
-class HipDetector:
+class HipDetector(PlanBacked):
     """kind: 'base' (YOLOX) | 'gl' (YOLOX + GL-fusion neck) | 'cross' (cross-scale head, new/yolox6.py) | 'cross10' (the
     same behind residual Patch_Conv_NonLocal_new blocks on dark3 / 4 / 5, new/yolox10.py).  state_dict uses the
     reference's key names (drone flavour).  dtype 'f16' (fp16 storage / fp32 accumulate,
@@ -26,8 +25,7 @@ class HipDetector:
     def __init__(self, kind: str, state_dict, dtype: str = "f16", device: str = "cuda:0", autotune: bool = False):
         self.kind, self.dtype, self.device, self.autotune = kind, dtype, device, autotune
         self.sd = {k: v.detach().cpu() for k, v in state_dict.items()}
-        self._compiled: Dict[Tuple, _Compiled] = {}
-        self._cache_lock = threading.Lock()       # plan cache: looked up / LRU-touched / evicted by several lanes' threads
+        super().__init__()                        # the plan cache: self._plans, its dict self._compiled
         self.num_classes = None
 
     # ------------------------------------------------------------------ compile
@@ -43,10 +41,9 @@ class HipDetector:
         `instance` > 0 builds an independent copy (own buffers, own stream) of the same plan, so
         consecutive batches can be in flight concurrently (see run_async)."""
         key = (n, H, W, tuple(sorted(post.items())) if post else None, use_graph, instance)
-        with self._cache_lock:
-            if key in self._compiled:
-                self._compiled[key] = self._compiled.pop(key)      # most recently used last
-                return self._compiled[key]
+        return self._plans.get(key, lambda: self._build(n, H, W, post, use_graph))
+
+    def _build(self, n: int, H: int, W: int, post: Optional[dict], use_graph: bool) -> _Compiled:
         if H % 32 or W % 32:
             raise ValueError("input H and W must be multiples of 32 (got %dx%d)" % (H, W))
         eng = Engine(self.dtype, self.device, autotune=self.autotune)
@@ -72,60 +69,12 @@ class HipDetector:
                 eng.nms(c.decoded, self.num_classes, post.get("mode", 0), post["conf_thres"], post["nms_thres"], c.nmsb)
                 if post.get("exchange_cap"):
                     eng.pack_detections(c.nmsb, int(post["exchange_cap"]))
-        eng.save_tune_cache()
-        c.graph_stream = None
-        if use_graph:
-            # one capture at a time, and no device-wide synchronisation around it: another host thread (a lane of
-            # the two-stage pipeline) may be capturing or launching -- a hipDeviceSynchronize issued while any
-            # stream captures invalidates that capture
-            with _lib.CAPTURE_LOCK:
-                c.plan.run()                     # warm-up outside capture (lazy module load, attributes)
-                torch.cuda.current_stream(eng.device).synchronize()
-                c.graph_stream = torch.cuda.Stream(device=eng.device)
-                with torch.cuda.stream(c.graph_stream):
-                    c.plan.capture(c.graph_stream)
-                c.graph_stream.synchronize()
-        # (two threads asking for the same key at once both build; the second insert wins, the first plan is dropped: correct, rare)
-        # LRU cap on resident plans (each holds its activations, an NMS workspace and, today, its own copy of the packed
-        # weights): the UFPMP fine stage compiles one plan per padded mosaic shape and lane -- without a cap HBM grows with
-        # every new shape over a data set.  GLSDET_MAX_PLANS (default 24) plans stay; evicted ones are rebuilt on demand.
-        import os as _os
-        cap = int(_os.environ.get("GLSDET_MAX_PLANS", "24"))
-        with self._cache_lock:
-            self._compiled[key] = c
-            while len(self._compiled) > max(1, cap):
-                self._compiled.pop(next(iter(self._compiled)))
-        return c
+        return self._finish(c, use_graph)
 
     # ------------------------------------------------------------------ run
     def run(self, c: _Compiled, img: Optional[torch.Tensor] = None, stream=None, scale: Optional[torch.Tensor] = None):
-        """One forward (+ post-processing if compiled in).  Asynchronous; a captured plan is
-        replayed on its own stream, ordered after/before the caller's current stream."""
-        if c.plan.captured:
-            st, cur = c.graph_stream, torch.cuda.current_stream()
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                if img is not None:
-                    c.img.copy_(img, non_blocking=True)
-                if scale is not None:
-                    c.scale.copy_(scale, non_blocking=True)
-                c.plan.launch(st)
-            cur.wait_stream(st)
-            return
-        if img is not None:
-            c.img.copy_(img, non_blocking=True)
-        if scale is not None:
-            c.scale.copy_(scale, non_blocking=True)
-        c.plan.run(stream)
-
-    @staticmethod
-    def run_async(c: _Compiled):
-        """Replay a captured plan on ITS OWN stream without ordering it against the caller's
-        current stream: with two instances alternating, the latency-bound tail of batch i
-        (NMS, small convs) overlaps the MFMA-bound body of batch i+1.  The caller synchronises
-        (torch.cuda.synchronize() or c.graph_stream.synchronize()) before reading results."""
-        assert c.plan.captured, "run_async needs compile(..., use_graph=True)"
-        c.plan.launch(c.graph_stream)
+        """One forward (+ post-processing if compiled in), see PlanBacked._replay."""
+        self._replay(c, stream, img=img, scale=scale)
 
     def forward_raw(self, img: torch.Tensor) -> List[torch.Tensor]:
         """Reference-shaped output: list of [B, 5+nc, H_l, W_l] fp32 logits (NCHW)."""

@@ -870,12 +870,16 @@ class Engine:
                                               out.data_ptr(), out.numel(), sf, _stream_ptr(self.stream)), "yolox_decode")
         return out
 
-    def nms_buffers(self, n: int, A: int, max_cand: int, max_det: int):
-        nbytes = self.lib.glsdet_nms_workspace_bytes(n, A, max_cand)
-        return {"ws": self.raw(nbytes), "n": n, "A": A, "max_cand": max_cand, "max_det": max_det,
+    def _result_buffers(self, ws_bytes: int, n: int, max_det: int, **extra):
+        """What every NMS flavour writes into: the workspace, dets [n, max_det, 7], count [2n] (kept per image, then found
+        per image) and the status word; `extra` = the sizes and inputs of the flavour."""
+        return {"ws": self.raw(ws_bytes), "n": n, "max_det": max_det, **extra,
                 "dets": torch.zeros(n, max_det, 7, dtype=torch.float32, device=self.device),
                 "count": torch.zeros(2 * n, dtype=torch.int32, device=self.device),
                 "status": torch.zeros(1, dtype=torch.int32, device=self.device)}
+
+    def nms_buffers(self, n: int, A: int, max_cand: int, max_det: int):
+        return self._result_buffers(self.lib.glsdet_nms_workspace_bytes(n, A, max_cand), n, max_det, A=A, max_cand=max_cand)
 
     def nms(self, pred: torch.Tensor, num_classes: int, box_mode: int, conf_thres: float, nms_thres: float, nb):
         n, A = pred.shape[0], pred.shape[1]
@@ -1029,21 +1033,23 @@ class Engine:
         return out
 
     def gfl_buffers(self, n: int, n_levels: int, max_cand: int, nms_pre: int, max_det: int):
-        nbytes = self.lib.glsdet_gfl_workspace_bytes(n, n_levels, max_cand, nms_pre)
-        return {"ws": self.raw(nbytes), "n": n, "max_cand": max_cand, "nms_pre": nms_pre, "max_det": max_det,
-                "dets": torch.zeros(n, max_det, 7, dtype=torch.float32, device=self.device),
-                "count": torch.zeros(2 * n, dtype=torch.int32, device=self.device),
-                "status": torch.zeros(1, dtype=torch.int32, device=self.device)}
+        return self._result_buffers(self.lib.glsdet_gfl_workspace_bytes(n, n_levels, max_cand, nms_pre), n, max_det,
+                                    max_cand=max_cand, nms_pre=nms_pre)
+
+    @staticmethod
+    def _gfl_levels(cls: Sequence[TView], reg: Sequence[TView], strides: Sequence[int], n: int,
+                    img_hw: Optional[torch.Tensor], scale_factors: Optional[torch.Tensor] = None):
+        """-> (cls views, reg views, strides, L) as the C arrays of glsdet_gfl_detect / glsdet_gfl_candidates; the optional
+        per-image rows img_hw [n, 2] and scale_factors [n, 4] are checked here."""
+        L = len(cls)
+        for t, k in ((img_hw, 2), (scale_factors, 4)):
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == k * n)
+        return ((View * L)(*[l.as_c() for l in cls]), (View * L)(*[l.as_c() for l in reg]), (C.c_int32 * L)(*strides), L)
 
     def gfl_detect(self, cls: Sequence[TView], reg: Sequence[TView], strides: Sequence[int], num_classes: int,
                    reg_max: int, in_h: int, in_w: int, score_thr: float, iou_thr: float, nb,
                    img_hw: Optional[torch.Tensor] = None, scale_factors: Optional[torch.Tensor] = None):
-        L = len(cls)
-        ca = (View * L)(*[l.as_c() for l in cls])
-        ra = (View * L)(*[l.as_c() for l in reg])
-        st = (C.c_int32 * L)(*strides)
-        for t, k in ((img_hw, 2), (scale_factors, 4)):
-            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == k * nb["n"])
+        ca, ra, st, L = self._gfl_levels(cls, reg, strides, nb["n"], img_hw, scale_factors)
         check(self.lib.glsdet_gfl_detect(ca, ra, L, st, num_classes, reg_max, in_h, in_w,
                                          img_hw.data_ptr() if img_hw is not None else None,
                                          scale_factors.data_ptr() if scale_factors is not None else None,
@@ -1071,11 +1077,7 @@ class Engine:
     def gfl_candidates(self, cls: Sequence[TView], reg: Sequence[TView], strides: Sequence[int], num_classes: int,
                        reg_max: int, in_h: int, in_w: int, score_thr: float, cb, img_hw: Optional[torch.Tensor] = None):
         """glsdet_gfl_candidates: get_bboxes(..., rescale=False, with_nms=False) into cb (gfl_candidate_buffers)."""
-        L = len(cls)
-        ca = (View * L)(*[l.as_c() for l in cls])
-        ra = (View * L)(*[l.as_c() for l in reg])
-        st = (C.c_int32 * L)(*strides)
-        assert img_hw is None or (img_hw.dtype == torch.float32 and img_hw.is_contiguous() and img_hw.numel() == 2 * cb["n"])
+        ca, ra, st, L = self._gfl_levels(cls, reg, strides, cb["n"], img_hw)
         check(self.lib.glsdet_gfl_candidates(ca, ra, L, st, num_classes, reg_max, in_h, in_w,
                                              img_hw.data_ptr() if img_hw is not None else None, score_thr,
                                              cb["nms_pre"], cb["max_cand"], cb["cand"].data_ptr(), cb["cap"],
@@ -1089,12 +1091,9 @@ class Engine:
         if nbytes <= 0:
             raise _lib.GlsdetError("aug_merge_nms: %d augmentations with candidate capacities summing to %d; at most %d "
                               "augmentations and 32768 candidates per image (lower nms_pre)" % (K, sum(caps), 12))
-        return {"ws": self.raw(nbytes), "n": n, "caps": tuple(caps), "max_det": max_det,
-                "meta": torch.zeros(K, n, 8, dtype=torch.float32, device=self.device),
-                "out_scale": torch.ones(n, 4, dtype=torch.float32, device=self.device),
-                "dets": torch.zeros(n, max_det, 7, dtype=torch.float32, device=self.device),
-                "count": torch.zeros(2 * n, dtype=torch.int32, device=self.device),
-                "status": torch.zeros(1, dtype=torch.int32, device=self.device)}
+        return self._result_buffers(nbytes, n, max_det, caps=tuple(caps),
+                                    meta=torch.zeros(K, n, 8, dtype=torch.float32, device=self.device),
+                                    out_scale=torch.ones(n, 4, dtype=torch.float32, device=self.device))
 
     def aug_merge_nms(self, cands: Sequence[torch.Tensor], counts: Sequence[torch.Tensor], iou_thr: float, mb,
                       use_out_scale: bool = False):
@@ -1121,11 +1120,7 @@ class Engine:
         if nbytes <= 0 or max_det < 1:
             raise _lib.GlsdetError("soft_nms: n %d, cap %d, max_det %d; need n >= 1, 1 <= cap <= 32768, max_det >= 1"
                                    % (n, cap, max_det))
-        return {"ws": self.raw(nbytes), "n": n, "cap": cap, "max_det": max_det,
-                "segment_limit": int(self.lib.glsdet_soft_nms_segment_limit()),
-                "dets": torch.zeros(n, max_det, 7, dtype=torch.float32, device=self.device),
-                "count": torch.zeros(2 * n, dtype=torch.int32, device=self.device),
-                "status": torch.zeros(1, dtype=torch.int32, device=self.device)}
+        return self._result_buffers(nbytes, n, max_det, cap=cap, segment_limit=int(self.lib.glsdet_soft_nms_segment_limit()))
 
     def soft_nms(self, cand: torch.Tensor, counts: torch.Tensor, num_classes: int, sb, method: str = "gaussian",
                  iou_thr: float = 0.3, sigma: float = 0.5, min_score: float = 1e-4, rescore: bool = False):

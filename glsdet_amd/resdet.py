@@ -17,7 +17,6 @@ Graph-level choices (all numerically the reference's arithmetic):
 """
 from __future__ import annotations
 
-import threading
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -25,8 +24,8 @@ import os
 
 import torch
 
-from . import _lib
 from .engine import Engine, F32, TView, fold_bn
+from .plans import PlanBacked
 
 # Width of the augmentation of the folded non-local associations ('gram' / 'pair': x' = [x ; 1 ; 0...], "C+a" in the comments
 # below).  One channel would do; 64 keeps the contraction length C+a a whole number of the conv kernels' 128-byte K steps
@@ -686,7 +685,7 @@ class _Compiled:
     __slots__ = ("img", "plan", "cls", "reg", "nb", "eng", "post", "graph_stream", "scale", "img_hw")
 
 
-class HipGflDetector:
+class HipGflDetector(PlanBacked):
     """ResNet-50 + FPN + GFLHead ('gfl') or MPHead ('mpdet'); mmdet state-dict names.
     cfg keys: start_level, num_outs, add_extra_convs, stacked_convs, strides, reg_max,
     proxies_list, gamma, depth, out_indices (defaults = the GFL r50-FPN / MPDet configs)."""
@@ -710,9 +709,8 @@ class HipGflDetector:
             self.num_classes = self.sd["bbox_head.gfl_cls.weight"].shape[0]
         else:
             self.num_classes = len(self.cfg["proxies_list"])
-        self._compiled: Dict[Tuple, _Compiled] = {}
-        self._aug: Dict[Tuple, dict] = {}         # detect_aug: private candidate buffers + merge buffers
-        self._cache_lock = threading.Lock()       # plan cache: looked up / LRU-touched / evicted by several lanes' threads
+        super().__init__()                        # the plan cache: self._plans, its dict self._compiled and its lock
+        self._aug: Dict[Tuple, dict] = {}         # detect_aug: private candidate buffers + merge buffers (under self._cache_lock)
 
     def _emit(self, eng: Engine, img: torch.Tensor, trace: Optional[dict] = None):
         b, c = ResDetBuilder(eng, self.sd), self.cfg
@@ -735,10 +733,9 @@ class HipGflDetector:
         (the reference's test_cfg keys, base_dense_head.py:168,295-298).  post = dict(score_thr, nms_pre, max_cand,
         with_nms=False) records the candidate exit instead (Engine.gfl_candidates): c.nb then holds cand / cand_count."""
         key = (n, H, W, tuple(sorted(post.items())) if post else None, use_graph, instance)
-        with self._cache_lock:
-            if key in self._compiled:
-                self._compiled[key] = self._compiled.pop(key)      # most recently used last
-                return self._compiled[key]
+        return self._plans.get(key, lambda: self._build(n, H, W, post, use_graph))
+
+    def _build(self, n: int, H: int, W: int, post: Optional[dict], use_graph: bool) -> _Compiled:
         eng = Engine(self.dtype, self.device, autotune=self.autotune)
         c = _Compiled()
         c.eng, c.post, c.nb, c.scale = eng, post, None, None
@@ -767,55 +764,11 @@ class HipGflDetector:
                                post["score_thr"], post["iou_thr"], c.nb, img_hw=c.img_hw, scale_factors=c.scale)
                 if post.get("exchange_cap"):
                     eng.pack_detections(c.nb, int(post["exchange_cap"]))
-        eng.save_tune_cache()
-        c.graph_stream = None
-        if use_graph:
-            # one capture at a time, and no device-wide synchronisation around it: another host thread (a lane of
-            # the two-stage pipeline) may be capturing or launching -- a hipDeviceSynchronize issued while any
-            # stream captures invalidates that capture
-            with _lib.CAPTURE_LOCK:
-                c.plan.run()                     # warm-up outside capture (lazy module load, attributes)
-                torch.cuda.current_stream(eng.device).synchronize()
-                c.graph_stream = torch.cuda.Stream(device=eng.device)
-                with torch.cuda.stream(c.graph_stream):
-                    c.plan.capture(c.graph_stream)
-                c.graph_stream.synchronize()
-        # (two threads asking for the same key at once both build; the second insert wins, the first plan is dropped: correct, rare)
-        # LRU cap on resident plans (each holds its activations, an NMS workspace and, today, its own copy of the packed
-        # weights): the UFPMP fine stage compiles one plan per padded mosaic shape and lane -- without a cap HBM grows with
-        # every new shape over a data set.  GLSDET_MAX_PLANS (default 24) plans stay; evicted ones are rebuilt on demand.
-        import os as _os
-        cap = int(_os.environ.get("GLSDET_MAX_PLANS", "24"))
-        with self._cache_lock:
-            self._compiled[key] = c
-            while len(self._compiled) > max(1, cap):
-                self._compiled.pop(next(iter(self._compiled)))
-        return c
+        return self._finish(c, use_graph)
 
     def run(self, c: _Compiled, img: Optional[torch.Tensor] = None, img_hw: Optional[torch.Tensor] = None,
             scale: Optional[torch.Tensor] = None):
-        def feed():
-            if img is not None:
-                c.img.copy_(img, non_blocking=True)
-            if img_hw is not None:
-                c.img_hw.copy_(img_hw, non_blocking=True)
-            if scale is not None:
-                c.scale.copy_(scale, non_blocking=True)
-        if c.plan.captured:
-            st, cur = c.graph_stream, torch.cuda.current_stream()
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                feed()
-                c.plan.launch(st)
-            cur.wait_stream(st)
-            return
-        feed()
-        c.plan.run(None)
-
-    @staticmethod
-    def run_async(c: _Compiled):
-        assert c.plan.captured, "run_async needs compile(..., use_graph=True)"
-        c.plan.launch(c.graph_stream)
+        self._replay(c, img=img, img_hw=img_hw, scale=scale)
 
     def forward_traced(self, img: torch.Tensor):
         """forward_raw emitted EAGERLY (no plan) with a snapshot of every stored tensor: (cls, reg, {store point: NCHW fp32})
