@@ -134,6 +134,41 @@ _SHARED_TUNED: dict = {}
 _TUNE_IO_LOCK = threading.Lock()       # save_tune_cache: lanes of one process share the table and the cache file
 
 
+def _in_geo(x: "TView") -> tuple:
+    """sizes and strides of a view: the input part of a tune-cache key"""
+    return (x.n, x.h, x.w, x.c, x.sn, x.sh, x.sw)
+
+
+def _out_geo(o: "TView") -> tuple:
+    """the output part of a tune-cache key (its n, h, w follow from the input and the conv)"""
+    return (o.c, o.sn, o.sh, o.sw)
+
+
+def _conv_desc(x: "TView", packed, stride: int, pad: int, act: str, out: "TView", res: Optional["TView"] = None,
+               tile_hint: int = 0, res_first: bool = False, d: Optional[ConvDesc] = None) -> ConvDesc:
+    """The glsdet_conv_desc of one conv (kernel size from `packed`); d: the struct to fill, an element of a ConvDesc array."""
+    d = ConvDesc() if d is None else d
+    d.x, d.y = x.as_c(), out.as_c()
+    d.res = res.as_c() if res is not None else View()
+    d.w, d.scale, d.bias = packed[0].data_ptr(), packed[1].data_ptr(), packed[2].data_ptr()
+    d.R, d.S, d.stride, d.pad, d.act, d.tile_hint = packed[4], packed[5], stride, pad, ACT[act], tile_hint
+    if res_first and res is not None:
+        d.act |= 0x100                          # GLSDET_ACT_RES_FIRST
+    return d
+
+
+def _fused_loses(us: float, parts) -> bool:
+    """The tuner's verdict on a fused launch of `us` microseconds against the launches it replaces (parts: their microseconds,
+    each tuned on its own): it must come within 3 % of their sum, plus the credit for the launch it removes.  `parts` is
+    consumed lazily; a part the tuner refused (None) ends the comparison and keeps the fused form."""
+    total = 0.0
+    for u in parts:
+        if u is None:
+            return False
+        total += u
+    return us > 0.97 * total + _fuse_credit_us()
+
+
 class _Ptr:
     """device address with the .data_ptr() of a tensor (a weight operand that lives in an activation buffer)"""
 
@@ -166,6 +201,7 @@ class Engine:
         if self._tune_cache_path and os.path.exists(self._tune_cache_path):
             with open(self._tune_cache_path) as f:
                 self._tuned.update({tuple(json.loads(k)): v for k, v in json.load(f).get(dtype, {}).items()})
+        self._tune_dirty = False        # save_tune_cache has something to write
         self._dtype_name = dtype
         self._vecs: dict = {}
         # verification (tools/variant_check.py): {"hint": h, "multi": h or None, "log": []} -- every conv also runs
@@ -212,34 +248,42 @@ class Engine:
         sc[:cout], bi[:cout] = scale, bias
         return (self.upload(flat.to(_TORCH_DT[self.dt])), self.upload(sc), self.upload(bi), cout, R, S)
 
+    # ---- the tuner
+    def _tune(self, key: tuple, measure) -> int:
+        """the tune table's entry for `key`; a miss stores what measure() returns"""
+        if key not in self._tuned:
+            self._tuned[key] = measure()
+            self._tune_dirty = True
+        return self._tuned[key]
+
+    def _measure(self, tune_fn, *args, must: str = ""):
+        """one `*_tune` entry point -> (rc, best variant, its microseconds); must: raise under that name when it refuses"""
+        best, us = C.c_int32(0), C.c_float(0)
+        rc = tune_fn(*args, _stream_ptr(self.stream), C.byref(best), C.byref(us))
+        if must:
+            check(rc, must)
+        return rc, best.value, us.value
+
+    def _conv_us(self, d: ConvDesc) -> Optional[float]:
+        """microseconds of the plain conv d on its best variant (glsdet_conv2d_tune), None when the tuner refuses it"""
+        rc, _, us = self._measure(self.lib.glsdet_conv2d_tune, C.byref(d))
+        return us if rc == 0 else None
+
     # ---- ops (each is one C-ABI call)
     def conv(self, x: TView, packed, stride: int, pad: int, act: str, out: Optional[TView] = None,
              res: Optional[TView] = None, out_dtype: Optional[int] = None, tile_hint: int = 0,
              res_first: bool = False) -> TView:
         """res_first: act(conv*scale + bias + res) (ResNet) instead of act(conv*scale + bias) + res."""
-        wdev, sdev, bdev, cout, R, S = packed
+        cout, R, S = packed[3:]
         ho = (x.h + 2 * pad - R) // stride + 1
         wo = (x.w + 2 * pad - S) // stride + 1
         if out is None:
             out = self.tensor(x.n, ho, wo, cout, out_dtype)
         assert out.c == ceil_to(cout, 8), (out.c, cout)
-        d = ConvDesc()
-        d.x, d.y = x.as_c(), out.as_c()
-        d.res = res.as_c() if res is not None else View()
-        d.w, d.scale, d.bias = wdev.data_ptr(), sdev.data_ptr(), bdev.data_ptr()
-        d.R, d.S, d.stride, d.pad, d.act, d.tile_hint = R, S, stride, pad, ACT[act], tile_hint
-        if res_first and res is not None:
-            d.act |= 0x100                      # GLSDET_ACT_RES_FIRST
+        d = _conv_desc(x, packed, stride, pad, act, out, res, tile_hint, res_first)
         if self.autotune and tile_hint == 0:
-            key = (x.n, x.h, x.w, x.c, x.sn, x.sh, x.sw, out.c, out.sn, out.sh, out.sw, R, S, stride, pad,
-                   res is not None, out.dtype)
-            if key not in self._tuned:
-                best, us = C.c_int32(0), C.c_float(0)
-                check(self.lib.glsdet_conv2d_tune(C.byref(d), _stream_ptr(self.stream), C.byref(best), C.byref(us)),
-                      "conv2d_tune")
-                self._tuned[key] = best.value
-                self._tune_dirty = True
-            d.tile_hint = self._tuned[key]
+            key = _in_geo(x) + _out_geo(out) + (R, S, stride, pad, res is not None, out.dtype)
+            d.tile_hint = self._tune(key, lambda: self._measure(self.lib.glsdet_conv2d_tune, C.byref(d), must="conv2d_tune")[1])
         sh = None
         if self.shadow is not None and tile_hint == 0 and self.shadow.get("hint"):
             sh = self._shadow_begin([d], [out], self.shadow["hint"], multi=False)
@@ -259,16 +303,10 @@ class Engine:
         -> out2 (glsdet_conv2d_chain).  Returns False, having launched nothing, when no kernel takes the fused problem
         (the caller then emits the two convs).  skip_y: nothing else reads `out` -- it is not stored (GLSDET_CHAIN_SKIP_Y;
         `out` is then only a scratch view for the tuner's comparison and the shadow check)."""
-        wdev, sdev, bdev, cout, R, S = packed
+        R, S = packed[4:]
         w2, s2, b2, cout2, R2, S2 = packed2
         assert R2 == 1 and S2 == 1 and out2.c == ceil_to(cout2, 8)
-        d = ConvDesc()
-        d.x, d.y = x.as_c(), out.as_c()
-        d.res = res.as_c() if res is not None else View()
-        d.w, d.scale, d.bias = wdev.data_ptr(), sdev.data_ptr(), bdev.data_ptr()
-        d.R, d.S, d.stride, d.pad, d.act, d.tile_hint = R, S, stride, pad, ACT[act], 0
-        if res_first and res is not None:
-            d.act |= 0x100
+        d = _conv_desc(x, packed, stride, pad, act, out, res, res_first=res_first)
         c = ConvChain()
         c.y2 = out2.as_c()
         c.w2, c.scale2, c.bias2 = w2.data_ptr(), s2.data_ptr(), b2.data_ptr()
@@ -276,29 +314,23 @@ class Engine:
         c.flags = 1 if skip_y else 0
         st = _stream_ptr(self.stream)
         if self.autotune:
-            key = ("chain", x.n, x.h, x.w, x.c, x.sn, x.sh, x.sw, out.c, out.sn, out.sh, out.sw, R, S, stride, pad,
-                   res is not None, out.dtype, c0, c.cin2, out2.c, out2.sn, out2.sh, out2.sw, bool(skip_y))
-            if key not in self._tuned:
-                best, us = C.c_int32(0), C.c_float(0)
-                rc = self.lib.glsdet_conv2d_chain_tune(C.byref(d), C.byref(c), st, C.byref(best), C.byref(us))
-                hint = best.value if rc == 0 else -1
+            key = ("chain",) + _in_geo(x) + _out_geo(out) + (R, S, stride, pad, res is not None, out.dtype, c0, c.cin2) + \
+                _out_geo(out2) + (bool(skip_y),)
+
+            def measure():
+                rc, best, us = self._measure(self.lib.glsdet_conv2d_chain_tune, C.byref(d), C.byref(c))
+                hint = best if rc == 0 else -1
                 if hint >= 0:
                     # fused only where it beats the two launches it replaces (each tuned on its own): the chained product
                     # runs in the tail of the producing workgroups, which costs more than a launch on some shapes
-                    b1, u1, b2h, u2 = C.c_int32(0), C.c_float(0), C.c_int32(0), C.c_float(0)
-                    d2 = ConvDesc()
-                    d2.x, d2.y, d2.res = out.channels(c0, c0 + cin2).as_c(), out2.as_c(), View()
-                    d2.w, d2.scale, d2.bias = w2.data_ptr(), s2.data_ptr(), b2.data_ptr()
-                    d2.R, d2.S, d2.stride, d2.pad, d2.act, d2.tile_hint = 1, 1, 1, 0, ACT[act2], 0
-                    if self.lib.glsdet_conv2d_tune(C.byref(d), st, C.byref(b1), C.byref(u1)) == 0 and \
-                            self.lib.glsdet_conv2d_tune(C.byref(d2), st, C.byref(b2h), C.byref(u2)) == 0 and \
-                            us.value > 0.97 * (u1.value + u2.value) + _fuse_credit_us():
+                    d2 = _conv_desc(out.channels(c0, c0 + cin2), packed2, 1, 0, act2, out2)
+                    if _fused_loses(us, (self._conv_us(dd) for dd in (d, d2))):
                         hint = -1
-                self._tuned[key] = hint
-                self._tune_dirty = True
-            if self._tuned[key] < 0:
+                return hint
+
+            d.tile_hint = self._tune(key, measure)
+            if d.tile_hint < 0:
                 return False
-            d.tile_hint = self._tuned[key]
         sh = None
         if self.shadow is not None and self.shadow.get("hint") and not skip_y:   # the variant under test computes y (unfused) first
             sh = self._shadow_begin([d], [out], self.shadow["hint"], multi=False)
@@ -310,10 +342,7 @@ class Engine:
             # and the chained product against a stand-alone 1x1 on the stored y: bit for bit
             ref = self.tensor(out2.n, out2.h, out2.w, out2.c, out2.dtype)
             self.conv(out.channels(c0, c0 + cin2), packed2, 1, 0, act2, out=ref, tile_hint=1)
-            a, b = out2.to_nchw(), ref.to_nchw()
-            self.shadow["log"].append({"shape": (x.n, out.h, out.w, cin2, out2.c, 1, 1), "scale": float(a.abs().max()),
-                                       "err": float((a - b).abs().max()), "nan": bool(torch.isnan(a).any()),
-                                       "differ": float((a != b).float().mean())})
+            self._shadow_record((x.n, out.h, out.w, cin2, out2.c, 1, 1), out2, ref)
         return ok
 
     def bottleneck(self, x: TView, packed1, act1: str, packed2, act2: str, out: TView, res: Optional[TView],
@@ -322,48 +351,32 @@ class Engine:
         halo of the 3x3's tiles and the hidden tensor never exists in memory.  `out` must not alias x.  Returns False,
         having launched nothing, when the fused kernel does not apply or (autotune) does not beat the two tuned launches
         it replaces; `hidden` is the scratch tensor the comparison (and the caller's fallback) uses."""
-        w1, s1, b1, cm, R1, S1 = packed1
-        w2, s2, b2, cout, R2, S2 = packed2
+        (cm, R1, S1), (cout, R2, S2) = packed1[3:], packed2[3:]
         if (R1, S1, R2, S2) != (1, 1, 3, 3) or cm != cout or cm not in (32, 64, 128) or x.dtype != out.dtype:
             return False
-        hid = hidden
-        d1, d2 = ConvDesc(), ConvDesc()
-        d1.x, d1.y, d1.res = x.as_c(), hid.as_c(), View()
-        d1.w, d1.scale, d1.bias = w1.data_ptr(), s1.data_ptr(), b1.data_ptr()
-        d1.R, d1.S, d1.stride, d1.pad, d1.act, d1.tile_hint = 1, 1, 1, 0, ACT[act1], 0
-        d2.x, d2.y = hid.as_c(), out.as_c()
-        d2.res = res.as_c() if res is not None else View()
-        d2.w, d2.scale, d2.bias = w2.data_ptr(), s2.data_ptr(), b2.data_ptr()
-        d2.R, d2.S, d2.stride, d2.pad, d2.act, d2.tile_hint = 3, 3, 1, 1, ACT[act2], 0
-        st = _stream_ptr(self.stream)
+        d1 = _conv_desc(x, packed1, 1, 0, act1, hidden)
+        d2 = _conv_desc(hidden, packed2, 1, 1, act2, out, res)
         hint = 0
         if self.autotune:
-            key = ("bneck", x.n, x.h, x.w, x.c, x.sn, x.sh, x.sw, cm, out.sn, out.sh, out.sw, res is not None, out.dtype)
-            if key not in self._tuned:
-                best, us = C.c_int32(0), C.c_float(0)
-                hint = best.value if self.lib.glsdet_bottleneck_tune(C.byref(d1), C.byref(d2), st, C.byref(best), C.byref(us)) == 0 else -1
-                if hint >= 0:
-                    hint = best.value
-                    # against the two launches it replaces, each tuned on its own
-                    h1, u1, h2, u2 = C.c_int32(0), C.c_float(0), C.c_int32(0), C.c_float(0)
-                    if self.lib.glsdet_conv2d_tune(C.byref(d1), st, C.byref(h1), C.byref(u1)) == 0 and \
-                            self.lib.glsdet_conv2d_tune(C.byref(d2), st, C.byref(h2), C.byref(u2)) == 0 and \
-                            us.value > 0.97 * (u1.value + u2.value) + _fuse_credit_us() and not os.environ.get("GLSDET_FORCE_BNECK"):
-                        hint = -1
-                self._tuned[key] = hint
-                self._tune_dirty = True
-            hint = self._tuned[key]
+            key = ("bneck",) + _in_geo(x) + (cm,) + _out_geo(out)[1:] + (res is not None, out.dtype)
+
+            def measure():
+                rc, best, us = self._measure(self.lib.glsdet_bottleneck_tune, C.byref(d1), C.byref(d2))
+                hint = best if rc == 0 else -1
+                # against the two launches it replaces, each tuned on its own
+                if hint >= 0 and _fused_loses(us, (self._conv_us(dd) for dd in (d1, d2))) and not os.environ.get("GLSDET_FORCE_BNECK"):
+                    hint = -1
+                return hint
+
+            hint = self._tune(key, measure)
             if hint < 0:
                 return False
-        ok = self.lib.glsdet_bottleneck(C.byref(d1), C.byref(d2), hint, st) == 0
+        ok = self.lib.glsdet_bottleneck(C.byref(d1), C.byref(d2), hint, _stream_ptr(self.stream)) == 0
         if ok and self.shadow is not None:      # against the two-launch form on the same operands: bit for bit
             ref = self.tensor(out.n, out.h, out.w, out.c, out.dtype)
             self.conv(x, packed1, 1, 0, act1, out=hidden, tile_hint=1)
             self.conv(hidden, packed2, 1, 1, act2, out=ref, res=res, tile_hint=1)
-            a, b = out.to_nchw(), ref.to_nchw()
-            self.shadow["log"].append({"shape": (x.n, out.h, out.w, cm, cm, 3, 3), "scale": float(a.abs().max()),
-                                       "err": float((a - b).abs().max()), "nan": bool(torch.isnan(a).any()),
-                                       "differ": float((a != b).float().mean())})
+            self._shadow_record((x.n, out.h, out.w, cm, cm, 3, 3), out, ref)
         return ok
 
     # ---- a whole CSPLayer (64 -> 64, hidden 32, one Bottleneck) as ONE launch (glsdet_csp_fused)
@@ -396,6 +409,10 @@ class Engine:
         launch(t, packs[2], 1, main, main if shortcut else None)
         launch(cat, packs[3], 0, out, None)
 
+    def _csp_key(self, xg, og, shortcut: bool) -> tuple:
+        """tune-cache key of the fused CSPLayer; xg / og = (n, h, w, c, sn, sh, sw) of its input / output view"""
+        return ("csp1",) + tuple(int(v) for v in xg) + tuple(int(v) for v in og) + (bool(shortcut), int(self.dt))
+
     def csp_fused_wins(self, xg, og, packs, shortcut: bool) -> bool:
         """Would Engine.csp_fused take the layer?  xg / og = (n, h, w, c, sn, sh, sw) of its input / output view (the input
         may not exist yet: the caller decides BEFORE it emits the layer's producer); packs = the packed convs conv1|conv2,
@@ -407,50 +424,32 @@ class Engine:
             return False
         if not self.autotune:
             return True
-        key = ("csp1",) + tuple(int(v) for v in xg) + tuple(int(v) for v in og) + (bool(shortcut), int(self.dt))
-        if key not in self._tuned:
+
+        def measure():
             x, out = self._tmp(*xg), self._tmp(*og)
-            st = _stream_ptr(self.stream)
-            d = self._csp_desc(x, out, packs, shortcut)
-            best, us = C.c_int32(0), C.c_float(0)
-            hint = best.value if self.lib.glsdet_csp_fused_tune(C.byref(d), st, C.byref(best), C.byref(us)) == 0 else -1
+            rc, best, us = self._measure(self.lib.glsdet_csp_fused_tune, C.byref(self._csp_desc(x, out, packs, shortcut)))
+            hint = best if rc == 0 else -1
             if hint >= 0:
-                sep = []
-
-                def tune(xi, pk, pad, o, res):
-                    dd = ConvDesc()
-                    dd.x, dd.y = xi.as_c(), o.as_c()
-                    dd.res = res.as_c() if res is not None else View()
-                    dd.w, dd.scale, dd.bias = pk[0].data_ptr(), pk[1].data_ptr(), pk[2].data_ptr()
-                    dd.R, dd.S, dd.stride, dd.pad, dd.act, dd.tile_hint = pk[4], pk[5], 1, pad, ACT["silu"], 0
-                    b, u = C.c_int32(0), C.c_float(0)
-                    sep.append(u.value if self.lib.glsdet_conv2d_tune(C.byref(dd), st, C.byref(b), C.byref(u)) == 0 else None)
-
-                self._csp_unfused(x, packs, shortcut, out, tune)
-                if None not in sep and us.value > 0.97 * sum(sep) + _fuse_credit_us():
+                sep = []            # all four are timed, also after one was refused
+                self._csp_unfused(x, packs, shortcut, out, lambda xi, pk, pad, o, res:
+                                  sep.append(self._conv_us(_conv_desc(xi, pk, 1, pad, "silu", o, res))))
+                if _fused_loses(us, sep):
                     hint = -1
-            self._tuned[key] = hint
-            self._tune_dirty = True
-        return self._tuned[key] >= 0
+            return hint
+
+        return self._tune(self._csp_key(xg, og, shortcut), measure) >= 0
 
     def csp_fused(self, x: TView, packs, shortcut: bool, out: TView) -> bool:
         """The CSPLayer x -> out in ONE launch (glsdet_csp_fused; packs as for csp_fused_wins): bit-identical to the four
         launches.  Returns False, having launched nothing, when the entry point refuses the operands."""
-        hint = 0
-        if self.autotune:
-            key = ("csp1", x.n, x.h, x.w, x.c, x.sn, x.sh, x.sw, out.n, out.h, out.w, out.c, out.sn, out.sh, out.sw,
-                   bool(shortcut), int(self.dt))
-            hint = max(self._tuned.get(key, 0), 0)
+        hint = max(self._tuned.get(self._csp_key(_in_geo(x), _in_geo(out), shortcut), 0), 0) if self.autotune else 0
         d = self._csp_desc(x, out, packs, shortcut)
         ok = self.lib.glsdet_csp_fused(C.byref(d), hint, _stream_ptr(self.stream)) == 0
         if ok and self.shadow is not None:      # against the four-launch form on the same operands: bit for bit
             ref = self._tmp(out.n, out.h, out.w, out.c)
             self._csp_unfused(x, packs, shortcut, ref,
                               lambda xi, pk, pad, o, res: self.conv(xi, pk, 1, pad, "silu", out=o, res=res, tile_hint=1))
-            a, b = out.to_nchw(), ref.to_nchw()
-            self.shadow["log"].append({"shape": (x.n, out.h, out.w, 64, 64, 3, 3), "scale": float(a.abs().max()),
-                                       "err": float((a - b).abs().max()), "nan": bool(torch.isnan(a).any()),
-                                       "differ": float((a != b).float().mean())})
+            self._shadow_record((x.n, out.h, out.w, 64, 64, 3, 3), out, ref)
         return ok
 
     def conv_multi(self, xs: Sequence[TView], packs, stride: int, pad: int, act: str,
@@ -464,14 +463,10 @@ class Engine:
         ress = list(ress) if ress is not None else [None] * n
         arr = (ConvDesc * n)()
         for i, (x, pk) in enumerate(zip(xs, packs)):
-            wdev, sdev, bdev, cout, R, S = pk
+            cout, R, S = pk[3:]
             if outs[i] is None:
                 outs[i] = self.tensor(x.n, (x.h + 2 * pad - R) // stride + 1, (x.w + 2 * pad - S) // stride + 1, cout, out_dtype)
-            d = arr[i]
-            d.x, d.y = x.as_c(), outs[i].as_c()
-            d.res = ress[i].as_c() if ress[i] is not None else View()
-            d.w, d.scale, d.bias = wdev.data_ptr(), sdev.data_ptr(), bdev.data_ptr()
-            d.R, d.S, d.stride, d.pad, d.act, d.tile_hint = R, S, stride, pad, ACT[act], tile_hint
+            _conv_desc(x, pk, stride, pad, act, outs[i], ress[i], tile_hint, d=arr[i])
         sh = None
         if self.shadow is not None and self.shadow.get("multi"):
             sh = self._shadow_begin([arr[i] for i in range(n)], outs, self.shadow["multi"], multi=True)
@@ -492,8 +487,8 @@ class Engine:
         glsdet_conv2d_multi: one argument block + the operand addresses of each problem), on the tile the tuner measures."""
         ress = list(ress) if ress is not None else [None] * len(xs)
         n = len(xs)
-        geo = lambda x, pk, o, r: (x.n, x.h, x.w, x.c, x.sn, x.sh, x.sw, x.dtype, pk[3], pk[4], pk[5], o.n, o.h, o.w, o.c, o.sn, o.sh,
-                                   o.sw, o.dtype) + ((-1, -1, -1, -1) if r is None else (r.sn, r.sh, r.sw, r.c))   # (flat: a tune-cache key)
+        geo = lambda x, pk, o, r: _in_geo(x) + (x.dtype, pk[3], pk[4], pk[5]) + _in_geo(o) + (o.dtype,) + \
+            ((-1, -1, -1, -1) if r is None else (r.sn, r.sh, r.sw, r.c))          # (flat: a tune-cache key)
         per = 8
         if n > 8 and stride == 1 and pad == 0 and packs[0][4] == 1 and packs[0][5] == 1 and not os.environ.get("GLSDET_NO_BATCH") and \
                 len({geo(x, pk, o, r) for x, pk, o, r in zip(xs, packs, outs, ress)}) == 1:
@@ -502,21 +497,13 @@ class Engine:
             k = min(per, n - i)
             hint = 0
             if k > 8 and self.autotune:
-                key = ("batch", k, act) + geo(xs[i], packs[i], outs[i], ress[i])
-                if key not in self._tuned:
+                def measure():
                     arr = (ConvDesc * k)()
                     for j in range(k):
-                        d, pk, r = arr[j], packs[i + j], ress[i + j]
-                        d.x, d.y = xs[i + j].as_c(), outs[i + j].as_c()
-                        d.res = r.as_c() if r is not None else View()
-                        d.w, d.scale, d.bias = pk[0].data_ptr(), pk[1].data_ptr(), pk[2].data_ptr()
-                        d.R, d.S, d.stride, d.pad, d.act, d.tile_hint = 1, 1, 1, 0, ACT[act], 0
-                    best, us = C.c_int32(0), C.c_float(0)
-                    check(self.lib.glsdet_conv2d_multi_tune(arr, k, _stream_ptr(self.stream), C.byref(best), C.byref(us)),
-                          "conv2d_multi_tune")
-                    self._tuned[key] = best.value
-                    self._tune_dirty = True
-                hint = self._tuned[key]
+                        _conv_desc(xs[i + j], packs[i + j], 1, 0, act, outs[i + j], ress[i + j], d=arr[j])
+                    return self._measure(self.lib.glsdet_conv2d_multi_tune, arr, k, must="conv2d_multi_tune")[1]
+
+                hint = self._tune(("batch", k, act) + geo(xs[i], packs[i], outs[i], ress[i]), measure)
             self.conv_multi(xs[i:i + k], packs[i:i + k], stride, pad, act, outs=outs[i:i + k], ress=ress[i:i + k], tile_hint=hint)
         return list(outs)
 
@@ -545,18 +532,15 @@ class Engine:
         rows = m.h * m.w
         assert m.n == 1 and m.sw == self.lib.glsdet_conv_kpad(1, 1, m.c, m.dtype), "as_weight needs an Engine.matrix view"
         cpad = self.lib.glsdet_conv_cout_pad(ceil_to(rows, 8))
-        if bias_dev is not None:
-            assert bias is None and bias_dev.dtype == F32 and bias_dev.sw >= cpad, "bias_dev: Engine.bias_vector of >= cout_pad floats"
-            key = ("vec", cpad, float(alpha))
-            if key not in self._vecs:
-                self._vecs[key] = (self.upload(torch.full((cpad,), float(alpha))), self.upload(torch.zeros(cpad)))
-            return (_Ptr(m.buf.data_ptr() + m.off * _ESIZE[m.dtype]), self._vecs[key][0],
-                    _Ptr(bias_dev.buf.data_ptr() + bias_dev.off * _ESIZE[F32]), ceil_to(rows, 8), 1, 1)
+        assert bias_dev is None or (bias is None and bias_dev.dtype == F32 and bias_dev.sw >= cpad), \
+            "bias_dev: Engine.bias_vector of >= cout_pad floats"
         key = ("vec", cpad, float(alpha))
         if key not in self._vecs:
             self._vecs[key] = (self.upload(torch.full((cpad,), float(alpha))), self.upload(torch.zeros(cpad)))
         sc, zero = self._vecs[key]
-        if bias is not None:
+        if bias_dev is not None:
+            zero = _Ptr(bias_dev.buf.data_ptr() + bias_dev.off * _ESIZE[F32])
+        elif bias is not None:
             bkey = ("bias", cpad, bias.data_ptr())
             if bkey not in self._vecs:
                 b = torch.zeros(cpad)
@@ -585,26 +569,20 @@ class Engine:
         if not self.autotune:
             small = all(o.n * o.h * o.w * o.c <= 64 * 64 * 384 for o in outs)
             return self.conv_multi(xs, packs, stride, pad, act, outs=outs, ress=ress) if small else separate()
-        key = ("multi", n, stride, pad, R, S) + tuple(v for x, o, r in zip(xs, outs, ress) for v in (
-            x.n, x.h, x.w, x.c, x.sn, x.sh, x.sw, o.c, o.sn, o.sh, o.sw, r is not None, o.dtype))
-        if key not in self._tuned:
+        key = ("multi", n, stride, pad, R, S) + tuple(v for x, o, r in zip(xs, outs, ress)
+                                                      for v in _in_geo(x) + _out_geo(o) + (r is not None, o.dtype))
+
+        def measure():
             arr = (ConvDesc * n)()
             single_us = 0.0
             for i, (x, pk, o, r) in enumerate(zip(xs, packs, outs, ress)):
-                d = arr[i]
-                d.x, d.y = x.as_c(), o.as_c()
-                d.res = r.as_c() if r is not None else View()
-                d.w, d.scale, d.bias = pk[0].data_ptr(), pk[1].data_ptr(), pk[2].data_ptr()
-                d.R, d.S, d.stride, d.pad, d.act, d.tile_hint = R, S, stride, pad, ACT[act], 0
-                best, us = C.c_int32(0), C.c_float(0)
-                check(self.lib.glsdet_conv2d_tune(C.byref(d), _stream_ptr(self.stream), C.byref(best), C.byref(us)), "conv2d_tune")
-                single_us += us.value
-            best, us = C.c_int32(0), C.c_float(0)
-            check(self.lib.glsdet_conv2d_multi_tune(arr, n, _stream_ptr(self.stream), C.byref(best), C.byref(us)),
-                  "conv2d_multi_tune")
-            self._tuned[key] = best.value if us.value < 0.95 * single_us + (n - 1) * _fuse_credit_us() else -1
-            self._tune_dirty = True
-        hint = self._tuned[key]
+                d = _conv_desc(x, pk, stride, pad, act, o, r, d=arr[i])
+                single_us += self._measure(self.lib.glsdet_conv2d_tune, C.byref(d), must="conv2d_tune")[2]
+            _, best, us = self._measure(self.lib.glsdet_conv2d_multi_tune, arr, n, must="conv2d_multi_tune")
+            # grouped only where it is 5 % under the n launches, each tuned on its own, plus the credit for those it removes
+            return best if us < 0.95 * single_us + (n - 1) * _fuse_credit_us() else -1
+
+        hint = self._tune(key, measure)
         if hint < 0:
             return separate()
         return self.conv_multi(xs, packs, stride, pad, act, outs=outs, ress=ress, tile_hint=hint)
@@ -632,9 +610,13 @@ class Engine:
         if state is None:
             return
         for shape, o, t in zip(*state):
-            a, b = o.to_nchw(), t.to_nchw()
-            self.shadow["log"].append({"shape": shape, "scale": float(a.abs().max()), "err": float((a - b).abs().max()),
-                                       "nan": bool(torch.isnan(b).any()), "differ": float((a != b).float().mean())})
+            self._shadow_record(shape, o, t, nan_in_ref=True)      # the variant under test is the `ref` side here
+
+    def _shadow_record(self, shape, got: TView, ref: TView, nan_in_ref: bool = False):
+        """One entry of shadow["log"]: how far `got` (the launch the plan keeps) is from `ref`, relative figures against got."""
+        a, b = got.to_nchw(), ref.to_nchw()
+        self.shadow["log"].append({"shape": shape, "scale": float(a.abs().max()), "err": float((a - b).abs().max()),
+                                   "nan": bool(torch.isnan(b if nan_in_ref else a).any()), "differ": float((a != b).float().mean())})
 
     def pack_dw(self, w: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor, c_pad: int):
         """depthwise weights [C,1,R,S] -> ([R*S][c_pad] in engine dtype, scale, bias, C, R, S)"""
@@ -655,15 +637,12 @@ class Engine:
         return out
 
     def dwconv(self, x: TView, packed, stride: int, pad: int, act: str, out: Optional[TView] = None, dilation: int = 1) -> TView:
-        wdev, sdev, bdev, C_, R, S = packed
+        R, S = packed[4:]
         ho = (x.h + 2 * pad - dilation * (R - 1) - 1) // stride + 1
         wo = (x.w + 2 * pad - dilation * (S - 1) - 1) // stride + 1
         if out is None:
             out = self.tensor(x.n, ho, wo, x.c, x.dtype)
-        d = ConvDesc()
-        d.x, d.y, d.res = x.as_c(), out.as_c(), View()
-        d.w, d.scale, d.bias = wdev.data_ptr(), sdev.data_ptr(), bdev.data_ptr()
-        d.R, d.S, d.stride, d.pad, d.act, d.tile_hint = R, S, stride, pad, ACT[act], 0
+        d = _conv_desc(x, packed, stride, pad, act, out)
         check(self.lib.glsdet_dwconv2d_dilated(C.byref(d), dilation, _stream_ptr(self.stream)), "dwconv2d")
         return out
 
@@ -986,7 +965,7 @@ class Engine:
         """3x3 stride-1 conv (no activation: GroupNorm follows) that also writes the GroupNorm partial sums of its output
         (glsdet_conv2d_gnstats).  -> (y, stats) or (y, None) when no statistics form applies or (autotune) the plain conv
         is faster by more than the statistics pass costs -- y is then produced by Engine.conv."""
-        wdev, sdev, bdev, cout, R, S = packed
+        cout, R, S = packed[3:]
         if out is None:
             out = self.tensor(x.n, x.h + 2 * pad - R + 1, x.w + 2 * pad - S + 1, cout)
         # Off unless GLSDET_GN_FUSION=1: measured (MPDet, 8 x 800 x 1344, A/B on one box) the statistics pass it saves costs
@@ -995,30 +974,22 @@ class Engine:
         if (R, S, pad) != (3, 3, 1) or x.dtype != out.dtype or not os.environ.get("GLSDET_GN_FUSION"):
             return self.conv(x, packed, 1, pad, "none", out=out), None
         stats = self.raw(self.lib.glsdet_conv2d_gnstats_bytes(out.n, out.h, out.w, groups))
-        d = ConvDesc()
-        d.x, d.y, d.res = x.as_c(), out.as_c(), View()
-        d.w, d.scale, d.bias = wdev.data_ptr(), sdev.data_ptr(), bdev.data_ptr()
-        d.R, d.S, d.stride, d.pad, d.act, d.tile_hint = 3, 3, 1, 1, ACT["none"], 8
-        st = _stream_ptr(self.stream)
+        d = _conv_desc(x, packed, 1, 1, "none", out, tile_hint=8)
         if self.autotune:
-            key = ("gnstats", x.n, x.h, x.w, x.c, x.sn, x.sh, x.sw, out.c, out.sn, out.sh, out.sw, groups, out.dtype)
-            if key not in self._tuned:
-                best, us = C.c_int32(0), C.c_float(0)
-                hint = -1
-                if self.lib.glsdet_conv2d_gnstats_tune(C.byref(d), groups, stats.data_ptr(), st, C.byref(best), C.byref(us)) == 0:
-                    hint = best.value
-                    # against the plain conv's best variant + the statistics pass it saves (one read of the output at ~4 TB/s)
-                    b1, u1 = C.c_int32(0), C.c_float(0)
-                    d.tile_hint = 0
-                    saved = out.n * out.h * out.w * out.c * _ESIZE[out.dtype] / 4e6
-                    if self.lib.glsdet_conv2d_tune(C.byref(d), st, C.byref(b1), C.byref(u1)) == 0 and us.value > u1.value + saved:
-                        hint = -1
-                self._tuned[key] = hint
-                self._tune_dirty = True
-            if self._tuned[key] < 0:
+            def measure():
+                rc, best, us = self._measure(self.lib.glsdet_conv2d_gnstats_tune, C.byref(d), groups, stats.data_ptr())
+                if rc != 0:
+                    return -1
+                # against the plain conv's best variant + the statistics pass it saves (one read of the output at ~4 TB/s)
+                d.tile_hint = 0
+                u1 = self._conv_us(d)
+                saved = out.n * out.h * out.w * out.c * _ESIZE[out.dtype] / 4e6
+                return -1 if u1 is not None and us > u1 + saved else best
+
+            d.tile_hint = self._tune(("gnstats",) + _in_geo(x) + _out_geo(out) + (groups, out.dtype), measure)
+            if d.tile_hint < 0:
                 return self.conv(x, packed, 1, pad, "none", out=out), None
-            d.tile_hint = self._tuned[key]
-        if self.lib.glsdet_conv2d_gnstats(C.byref(d), groups, stats.data_ptr(), st) != 0:
+        if self.lib.glsdet_conv2d_gnstats(C.byref(d), groups, stats.data_ptr(), _stream_ptr(self.stream)) != 0:
             return self.conv(x, packed, 1, pad, "none", out=out), None
         return out, stats
 
@@ -1150,7 +1121,7 @@ class Engine:
         check(self.lib.glsdet_plan_set_branch(b), "plan_set_branch")
 
     def save_tune_cache(self):
-        if not self._tune_cache_path or not getattr(self, "_tune_dirty", False):
+        if not self._tune_cache_path or not self._tune_dirty:
             return
         with _TUNE_IO_LOCK:                         # other lanes' tuners insert into the shared table meanwhile: snapshot it
             data = {}

@@ -474,7 +474,8 @@ def test_conv2d_multi_batched_form_equals_separate_convs(engines, mode, case):
 
 def test_tune_cache_keys_of_every_tuned_form_survive_the_json_file(tmp_path, monkeypatch):
     """The tuning table is keyed by flat tuples and stored as JSON (GLSDET_TUNE_CACHE): a second engine must load what the
-    first one measured -- single convs, grouped launches, the batched form with and without a residual -- key for key."""
+    first one measured -- single convs, grouped launches, the batched form with and without a residual, and the verdicts
+    on the fused forms (chain, bottleneck, CSPLayer: a variant or -1, which is the tuner's business) -- key for key."""
     from glsdet_amd.engine import Engine
     monkeypatch.setenv("GLSDET_TUNE_CACHE", str(tmp_path / "tune.json"))
     eng = Engine("f16", autotune=True)
@@ -486,9 +487,17 @@ def test_tune_cache_keys_of_every_tuned_form_survive_the_json_file(tmp_path, mon
         eng.conv_many(xs, pk, 1, 0, "none", [eng.tensor(1, 6, 11, 40) for _ in range(12)], ress=ress)
     eng.conv_group(xs[:3], pk[:3], 1, 0, "relu")
     eng.conv(xs[0], pk[0], 1, 0, "relu")
+    pack = lambda co, ci, k: eng.pack_conv([(torch.randn(co, ci, k, k, generator=g) / (3 * k), torch.ones(co), torch.zeros(co))], ci)
+    p3, p1, p40 = pack(64, 64, 3), pack(64, 64, 1), pack(40, 32, 1)
+    y64 = eng.tensor(1, 6, 11, 64)
+    eng.conv_chain(xs[0], p3, 1, 1, "silu", y64, None, p40, "silu", 32, 32, eng.tensor(1, 6, 11, 40))
+    eng.bottleneck(xs[0], p1, "silu", p3, "silu", y64, None, eng.tensor(1, 6, 11, 64))
+    geo = lambda v: (v.n, v.h, v.w, v.c, v.sn, v.sh, v.sw)
+    eng.csp_fused_wins(geo(xs[0]), geo(y64), [p1, pack(32, 32, 1), pack(32, 32, 3), pack(64, 64, 1)], True)
     torch.cuda.synchronize()
     eng.save_tune_cache()
     assert sum(1 for k in eng._tuned if k[0] == "batch") >= 2
+    assert {k[0] for k in eng._tuned} >= {"chain", "bneck", "csp1"}
     import json
     with open(tmp_path / "tune.json") as f:
         loaded = {tuple(json.loads(k)): v for k, v in json.load(f)["f16"].items()}        # (Engine.__init__'s own parse)
