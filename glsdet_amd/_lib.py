@@ -68,6 +68,10 @@ _SIGS = {
     "glsdet_conv2d_multi_tune": (C.c_int, [C.POINTER(ConvDesc), C.c_int32, C.c_void_p, C.POINTER(C.c_int32),
                                            C.POINTER(C.c_float)]),
     "glsdet_conv2d_tune": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "glsdet_conv2d_grouped": (C.c_int, [C.POINTER(ConvDesc), C.c_int32, C.c_void_p]),
+    "glsdet_conv_grouped_weight_elems": (C.c_int64, [C.c_int32, C.c_int32]),
+    "glsdet_conv2d_grouped_tune": (C.c_int, [C.POINTER(ConvDesc), C.c_int32, C.c_void_p, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_float)]),
     "glsdet_dwconv2d": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
     "glsdet_dwconv2d_dilated": (C.c_int, [C.POINTER(ConvDesc), C.c_int32, C.c_void_p]),
     "glsdet_gate": (C.c_int, [C.POINTER(View), C.POINTER(View), C.POINTER(View), C.POINTER(View), C.c_int32, C.c_void_p]),

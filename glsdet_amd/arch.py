@@ -193,8 +193,14 @@ def _bn(t: "_Table", p: str, c: int):
     t[p + ".num_batches_tracked"] = ()
 
 
-def resnet_table(t: "_Table", p: str, depth: int = 50, base: int = 64):
-    """torchvision-style names, resnet.py:571-598 (stem) and res_layer.py (stages)."""
+def resnext_width(planes: int, groups: int = 1, base_width: int = 4, base: int = 64) -> int:
+    """channels of conv1's output / conv2 of a Bottleneck (resnext.py:29-33); groups == 1: planes (ResNet)"""
+    return planes if groups == 1 else (planes * base_width // base) * groups
+
+
+def resnet_table(t: "_Table", p: str, depth: int = 50, base: int = 64, groups: int = 1, base_width: int = 4):
+    """torchvision-style names, resnet.py:571-598 (stem) and res_layer.py (stages).  groups > 1: ResNeXt (resnext.py:12-85:
+    the same names in the same order, conv1 / conv2 of width floor(planes * base_width / base) * groups, conv2 grouped)."""
     t[p + ".conv1.weight"] = (base, 3, 7, 7)
     _bn(t, p + ".bn1", base)
     inplanes = base
@@ -202,11 +208,12 @@ def resnet_table(t: "_Table", p: str, depth: int = 50, base: int = 64):
         planes = base * 2 ** i
         for j in range(nblocks):
             q = "%s.layer%d.%d" % (p, i + 1, j)
-            t[q + ".conv1.weight"] = (planes, inplanes, 1, 1)
-            _bn(t, q + ".bn1", planes)
-            t[q + ".conv2.weight"] = (planes, planes, 3, 3)
-            _bn(t, q + ".bn2", planes)
-            t[q + ".conv3.weight"] = (planes * 4, planes, 1, 1)
+            width = resnext_width(planes, groups, base_width, base)
+            t[q + ".conv1.weight"] = (width, inplanes, 1, 1)
+            _bn(t, q + ".bn1", width)
+            t[q + ".conv2.weight"] = (width, width // groups, 3, 3)
+            _bn(t, q + ".bn2", width)
+            t[q + ".conv3.weight"] = (planes * 4, width, 1, 1)
             _bn(t, q + ".bn3", planes * 4)
             if j == 0:                      # stride != 1 or inplanes != planes*4 (res_layer.py:40)
                 t[q + ".downsample.0.weight"] = (planes * 4, inplanes, 1, 1)
@@ -282,13 +289,15 @@ def mp_head_table(t: "_Table", p: str, proxies_list, in_channels: int = 256, fea
 def resdet_state_dict_shapes(kind: str, num_classes: int = 10, depth: int = 50, start_level: int = 1,
                              num_outs: int = 5, add_extra_convs="on_output", stacked: int = 4, reg_max: int = 16,
                              proxies_list=(2, 3, 2, 5, 4, 8, 8, 4, 3, 3), gl_fusion: bool = False,
-                             gl_levels=(1, 2, 3), gl_channel_cat: str = "linear") -> "OrderedDict[str, Tuple[int, ...]]":
+                             gl_levels=(1, 2, 3), gl_channel_cat: str = "linear", groups: int = 1,
+                             base_width: int = 4) -> "OrderedDict[str, Tuple[int, ...]]":
     """kind 'gfl': GFL r50-FPN (SingleStageDetector: backbone / neck / bbox_head); 'mpdet': MPDet.
-    gl_fusion: the neck is a GLFusionFPN (plug-ins neck.gl_fusion.<i> on the backbone outputs gl_levels)."""
+    gl_fusion: the neck is a GLFusionFPN (plug-ins neck.gl_fusion.<i> on the backbone outputs gl_levels).
+    groups > 1: the backbone is a ResNeXt (groups x base_width d)."""
     if kind not in ("gfl", "mpdet"):
         raise ValueError("kind must be 'gfl' or 'mpdet'")
     t = _Table()
-    resnet_table(t, "backbone", depth)
+    resnet_table(t, "backbone", depth, groups=groups, base_width=base_width)
     fpn_table(t, "neck", [256, 512, 1024, 2048], 256, start_level, num_outs, add_extra_convs)
     if gl_fusion:
         for i in gl_levels:

@@ -964,8 +964,8 @@ static int time_variants(std::vector<OpRecord>& ops, const std::vector<int>& ids
 }
 
 // the tail of every *_tune entry point: time the candidates, report the fastest id
-static int tune_report(std::vector<OpRecord>& ops, const std::vector<int>& ids, void* stream, const char* none_applies,
-                       int32_t* best_hint, float* best_us) {
+int glsdet::tune_report(std::vector<OpRecord>& ops, const std::vector<int>& ids, void* stream, const char* none_applies,
+                        int32_t* best_hint, float* best_us) {
   float best = 1e30f;
   int bh = 0, any = 0;
   int rc = time_variants(ops, ids, (hipStream_t)stream, &bh, &best, &any);

@@ -2,6 +2,7 @@
 // stride-1 kxk with the input patch staged once per channel chunk).
 #pragma once
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
 
@@ -797,5 +798,8 @@ int conv_bneck_try(const BneckArgs& b, int dt, int hint, OpRecord* op);
 int conv1x1_ws_try(const ConvArgs& a, int xdt, int ydt, OpRecord* op);
 // persistent LDS-DMA GEMM kernel for 1x1 convs (conv_gemm.hip), tile_hint 16 + variant; returns 1 if it does not apply
 int conv_gemm_try(const ConvArgs& a, int xdt, int ydt, const TileHint& hint, OpRecord* op);
+// the tail of the *_tune entry points (conv.hip): times the candidate ops on the device, reports the fastest id and its time
+int tune_report(std::vector<OpRecord>& ops, const std::vector<int>& ids, void* stream, const char* none_applies,
+                int32_t* best_hint, float* best_us);
 
 }  // namespace glsdet

@@ -179,6 +179,57 @@ class _Ptr:
         return self._p
 
 
+def expand_grouped_weight(w: torch.Tensor, groups: int) -> torch.Tensor:
+    """grouped weights [C, Cg, R, S] -> the block-diagonal dense [C, C, R, S] (zeros outside each group's Cg x Cg block)"""
+    c, cg = w.shape[0], w.shape[1]
+    assert c == groups * cg, (tuple(w.shape), groups)
+    dense = torch.zeros(c, c, w.shape[2], w.shape[3], dtype=w.dtype)
+    for g in range(groups):
+        dense[g * cg:(g + 1) * cg, g * cg:(g + 1) * cg] = w[g * cg:(g + 1) * cg]
+    return dense
+
+
+class GroupedPack:
+    """Weights of one grouped 3x3 conv (Engine.pack_conv_grouped), uploaded in the form that is asked for, once:
+    blocks() -- the `packed` tuple of the grouped kernel, None where it refuses the group width; dense() -- the `packed` tuple
+    of the block-diagonal dense conv.  The engine that made it owns the uploads.  The fp32 host weights stay: either form may
+    still be asked for (another geometry's tuner verdict, the shadow check)."""
+
+    def __init__(self, eng: "Engine", w: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor, groups: int):
+        c, cg, R, S = w.shape
+        assert (R, S) == (3, 3) and c == groups * cg and c % 8 == 0, (tuple(w.shape), groups)
+        self.eng, self.groups, self.c, self.cg = eng, groups, c, cg
+        self.kernel_takes = eng.lib.glsdet_conv_grouped_weight_elems(groups, cg) > 0
+        self._host = (w, scale, bias)
+        self._blocks = self._dense = None
+
+    def blocks(self):
+        if self._blocks is None and self.kernel_takes:
+            from .torch_ops import grouped_weight_blocks
+            w, scale, bias = self._host
+            cpad = ceil_to(self.c, 32)
+            sc, bi = torch.ones(cpad), torch.zeros(cpad)
+            sc[:self.c], bi[:self.c] = scale, bias
+            up = self.eng.upload
+            self._blocks = (up(grouped_weight_blocks(w).to(_TORCH_DT[self.eng.dt])), up(sc), up(bi), self.c, 3, 3)
+        return self._blocks
+
+    def dense(self, keep: bool = True):
+        """keep=False: a pack the CALLER owns (a tuner comparison holds it while it measures); adopt() makes it the cached one"""
+        if self._dense is not None:
+            return self._dense
+        w, scale, bias = self._host
+        pk = self.eng.pack_conv([(expand_grouped_weight(w, self.groups), scale, bias)], self.c, keep=keep)
+        if keep:
+            self._dense = pk
+        return pk
+
+    def adopt(self, pk):
+        if self._dense is None:
+            self.eng.keep(pk[:3])
+            self._dense = pk
+
+
 class Engine:
     """Owns device buffers and packed weights; emits ops (eagerly or into a Plan)."""
 
@@ -222,16 +273,22 @@ class Engine:
         buf = self.raw(n * h * w * cp * _ESIZE[dt])
         return TView(buf, 0, n, h, w, cp, h * w * cp, w * cp, cp, dt)
 
-    def upload(self, arr: torch.Tensor) -> torch.Tensor:
+    def upload(self, arr: torch.Tensor, keep: bool = True) -> torch.Tensor:
+        """keep=False: the caller owns the device tensor (it is freed with the caller's last reference)"""
         t = arr.contiguous().to(self.device)
-        self._keep.append(t)
-        self.alloc_bytes += t.numel() * t.element_size()
+        if keep:
+            self.keep([t])
         return t
 
+    def keep(self, tensors) -> None:
+        for t in tensors:
+            self._keep.append(t)
+            self.alloc_bytes += t.numel() * t.element_size()
+
     # ---- weights
-    def pack_conv(self, parts: Sequence[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]], cin_pad: int):
+    def pack_conv(self, parts: Sequence[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]], cin_pad: int, keep: bool = True):
         """parts: [(w OIHW fp32, scale[O], bias[O])...] concatenated along O.
-        -> (w_dev [cout_pad][kpad] in engine dtype, scale_dev, bias_dev, cout, R, S)"""
+        -> (w_dev [cout_pad][kpad] in engine dtype, scale_dev, bias_dev, cout, R, S); keep: as Engine.upload"""
         w = torch.cat([p[0].float() for p in parts], 0)
         scale = torch.cat([p[1].float() for p in parts], 0)
         bias = torch.cat([p[2].float() for p in parts], 0)
@@ -246,7 +303,7 @@ class Engine:
         sc = torch.ones(cpad, dtype=torch.float32)
         bi = torch.zeros(cpad, dtype=torch.float32)
         sc[:cout], bi[:cout] = scale, bias
-        return (self.upload(flat.to(_TORCH_DT[self.dt])), self.upload(sc), self.upload(bi), cout, R, S)
+        return (self.upload(flat.to(_TORCH_DT[self.dt]), keep), self.upload(sc, keep), self.upload(bi, keep), cout, R, S)
 
     # ---- the tuner
     def _tune(self, key: tuple, measure) -> int:
@@ -644,6 +701,54 @@ class Engine:
             out = self.tensor(x.n, ho, wo, x.c, x.dtype)
         d = _conv_desc(x, packed, stride, pad, act, out)
         check(self.lib.glsdet_dwconv2d_dilated(C.byref(d), dilation, _stream_ptr(self.stream)), "dwconv2d")
+        return out
+
+    # ---- grouped 3x3 conv (ResNeXt conv2; glsdet_conv2d_grouped)
+    def pack_conv_grouped(self, parts: Sequence[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]], groups: int) -> "GroupedPack":
+        """parts: [(w [O, Cg, 3, 3] fp32, scale[O], bias[O])...] concatenated along O (O sums to groups * Cg).  Nothing is
+        uploaded yet: the block layout of glsdet_conv2d_grouped (GroupedPack.blocks) and the block-diagonal dense pack
+        (GroupedPack.dense: Engine.pack_conv over all C input channels) each when something first asks for it."""
+        w = torch.cat([p[0].float() for p in parts], 0)
+        scale = torch.cat([p[1].float() for p in parts], 0)
+        bias = torch.cat([p[2].float() for p in parts], 0)
+        return GroupedPack(self, w, scale, bias, groups)
+
+    def conv_grouped(self, x: TView, packed: "GroupedPack", stride: int, act: str, out: Optional[TView] = None,
+                     expand: Optional[bool] = None) -> TView:
+        """act(scale * conv3x3_grouped(x) + bias), pad 1.  expand=True: as the block-diagonal dense conv through Engine.conv
+        (C / Cg times the multiplies: the only form for a group width the kernel refuses, and the A/B partner of
+        measurements); None: the grouped kernel where it takes the width -- under autotune only where it is not slower
+        than the expansion on its tuned best variant (tuner key ("grouped", ...))."""
+        assert x.c == packed.c, (x.c, packed.c)
+        ho, wo = (x.h - 1) // stride + 1, (x.w - 1) // stride + 1
+        if out is None:
+            out = self.tensor(x.n, ho, wo, x.c, x.dtype)
+        if expand is None:
+            expand = not packed.kernel_takes
+            if not expand and self.autotune:
+                key = ("grouped",) + _in_geo(x) + _out_geo(out) + (packed.groups, stride, out.dtype)
+
+                def measure():
+                    d = _conv_desc(x, packed.blocks(), stride, 1, act, out)
+                    rc, _, us = self._measure(self.lib.glsdet_conv2d_grouped_tune, C.byref(d), packed.groups)
+                    if rc != 0:
+                        return -1
+                    dense = packed.dense(keep=False)            # held here until the tuner has run on it
+                    dense_us = self._conv_us(_conv_desc(x, dense, stride, 1, act, out))
+                    if dense_us is None or us <= dense_us:
+                        return 0
+                    packed.adopt(dense)                         # the expansion stays: the pack that was measured is the one kept
+                    return -1
+
+                expand = self._tune(key, measure) < 0
+        if expand:
+            return self.conv(x, packed.dense(), stride, 1, act, out=out)
+        d = _conv_desc(x, packed.blocks(), stride, 1, act, out)
+        check(self.lib.glsdet_conv2d_grouped(C.byref(d), packed.groups, _stream_ptr(self.stream)), "conv2d_grouped")
+        if self.shadow is not None:             # against the block-diagonal expansion on the generic kernel
+            ref = self.tensor(out.n, out.h, out.w, out.c, out.dtype)
+            self.conv(x, packed.dense(), stride, 1, act, out=ref, tile_hint=1)
+            self._shadow_record((x.n, out.h, out.w, x.c, x.c, 3, stride), out, ref)
         return out
 
     def focus_pack(self, img: torch.Tensor, out: Optional[TView] = None) -> TView:

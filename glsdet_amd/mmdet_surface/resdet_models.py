@@ -1,10 +1,10 @@
-"""mmdet-flavour surface of the ResNet-50 + FPN + GFLHead / MPHead detectors: the classes the
+"""mmdet-flavour surface of the ResNet / ResNeXt + FPN + GFLHead / MPHead detectors: the classes the
 UFPMP-Det configs name (`type='GFL'` coarse detector, `type='MPDet'` fine detector,
 ufp/ufpmp_det_eval.py:218-227) with the reference's constructor arguments, state_dict names,
 call convention and result format.  Arithmetic = the libglsdet_hip plan of
 glsdet_amd.resdet.HipGflDetector.
 
-Reference: ufp/mmdet/models/backbones/resnet.py:306-470, necks/fpn.py:62-148,
+Reference: ufp/mmdet/models/backbones/resnet.py:306-470, backbones/resnext.py, necks/fpn.py:62-148,
 dense_heads/gfl_head.py:87-152, dense_heads/mp_head.py:23-91, dense_heads/anchor_head.py,
 detectors/{single_stage.py:19-108, mpdet.py, base.py:157-175}, core/bbox/transforms.py:116-133.
 """
@@ -16,7 +16,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..arch import _Table, fpn_table, gfl_head_table, gl_fusion_table, mp_head_table, resnet_table, RESNET_STAGE_BLOCKS
+from ..arch import _Table, fpn_table, gfl_head_table, gl_fusion_table, mp_head_table, resnet_table, resnext_width, RESNET_STAGE_BLOCKS
 from ..drone.body import TableModule, _autotune
 from ..resdet import HipGflDetector
 from .registry import BACKBONES, DETECTORS, HEADS, NECKS, ConfigDict, build_backbone, build_head, build_neck
@@ -32,7 +32,8 @@ class ResNet(TableModule):
                  dilations=(1, 1, 1, 1), out_indices=(0, 1, 2, 3), style="pytorch", deep_stem=False, avg_down=False,
                  frozen_stages=-1, conv_cfg=None, norm_cfg=dict(type="BN", requires_grad=True), norm_eval=True, dcn=None,
                  stage_with_dcn=(False, False, False, False), plugins=None, with_cp=False, zero_init_residual=True,
-                 pretrained=None, init_cfg=None):
+                 pretrained=None, init_cfg=None, _groups=1, _base_width=4):
+        """_groups / _base_width: how the ResNeXt subclass hands its two arguments to the table (not config keys)"""
         super().__init__()
         if depth not in (18, 34, 50, 101, 152):
             raise KeyError("invalid depth %s for resnet" % depth)
@@ -52,8 +53,26 @@ class ResNet(TableModule):
         self.depth, self.out_indices = depth, tuple(out_indices)
         self.out_channels = [256, 512, 1024, 2048]
         t = _Table()
-        resnet_table(t, "x", depth)
+        if _groups > 1 and resnext_width(base_channels, _groups, _base_width, base_channels) % 8:
+            raise NotImplementedError("ResNeXt(groups=%r, base_width=%r) is not lowered: the stage-1 width must be a multiple "
+                                      "of 8" % (_groups, _base_width))
+        resnet_table(t, "x", depth, base_channels, groups=_groups, base_width=_base_width)
         self._init_table(_Table((k[2:], v) for k, v in t.items()))
+
+
+@BACKBONES.register_module()
+class ResNeXt(ResNet):
+    """ufp/mmdet/models/backbones/resnext.py:109-154: a ResNet whose Bottlenecks run conv1 / conv2 at width
+    floor(planes * base_width / base_channels) * groups, conv2 as a 3x3 conv of `groups` groups (:29-33, :55-64).  Same
+    state-dict names and order, same refusals as ResNet (depth 152, caffe style, DCN, plugins: NotImplementedError)."""
+
+    def __init__(self, groups=1, base_width=4, **kwargs):
+        if int(groups) != groups or groups < 1 or int(base_width) != base_width or base_width < 1:
+            raise ValueError("ResNeXt(groups=%r, base_width=%r): positive integers" % (groups, base_width))
+        if "_groups" in kwargs or "_base_width" in kwargs:
+            raise TypeError("ResNeXt takes groups= and base_width=")
+        super().__init__(_groups=int(groups), _base_width=int(base_width), **kwargs)
+        self.groups, self.base_width = int(groups), int(base_width)
 
 
 @NECKS.register_module()
@@ -218,7 +237,8 @@ class SingleStageDetector(nn.Module):
             kind = "mpdet" if isinstance(h, MPHead) else "gfl"
             cfg = dict(start_level=n.start_level, num_outs=n.num_outs, add_extra_convs=n.add_extra_convs,
                        stacked_convs=h.stacked_convs, strides=h.strides, reg_max=h.reg_max, depth=self.backbone.depth,
-                       out_indices=self.backbone.out_indices)
+                       out_indices=self.backbone.out_indices, groups=getattr(self.backbone, "groups", 1),
+                       base_width=getattr(self.backbone, "base_width", 4))
             if kind == "mpdet":
                 cfg.update(proxies_list=tuple(h.proxies_list), gamma=float(h.gamma))
             cfg.update(gl_levels=list(n.gl_levels) if isinstance(n, GLFusionFPN) else [])

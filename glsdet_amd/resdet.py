@@ -24,6 +24,7 @@ import os
 
 import torch
 
+from .arch import resnext_width
 from .engine import Engine, F32, TView, fold_bn
 from .plans import PlanBacked
 
@@ -93,6 +94,21 @@ class ResDetBuilder:
         return self._packed[key]
 
     # ------------------------------------------------------------------ backbone
+    def _conv2(self, p: str, t: TView, stride: int, out: Optional[TView] = None) -> TView:
+        """relu(bn2(conv2(t))) of a Bottleneck.  The group count is read off conv2.weight: dense (ResNet) as ever; grouped
+        (ResNeXt, resnext.py:55-64) on the grouped kernel (Engine.conv_grouped), or -- GLSDET_NO_GROUPED_CONV=1, the A/B switch,
+        and group widths the kernel refuses -- as the block-diagonal dense conv."""
+        e, w = self.e, self.sd[p + ".conv2.weight"]
+        if w.shape[1] == t.c:
+            return e.conv(t, self._pack(p + ".conv2", [self._bn_part(p + ".conv2", p + ".bn2")], t.c), stride, 1, "relu", out=out)
+        if w.shape[0] != t.c or t.c % w.shape[1] or tuple(w.shape[2:]) != (3, 3):
+            raise ValueError("%s.conv2.weight %s is no grouped 3x3 conv over %d channels" % (p, tuple(w.shape), t.c))
+        key = (p + ".conv2", "grouped")
+        if key not in self._packed:
+            self._packed[key] = e.pack_conv_grouped([self._bn_part(p + ".conv2", p + ".bn2")], t.c // w.shape[1])
+        return e.conv_grouped(t, self._packed[key], stride, "relu", out=out,
+                              expand=True if os.environ.get("GLSDET_NO_GROUPED_CONV") else None)
+
     def bottleneck(self, p: str, x: TView, stride: int, cat: Optional[TView] = None) -> TView:
         """resnet.py:263-303 (style='pytorch': the stride sits on the 3x3).
         cat: a [n, h, w, mid + cin] buffer whose channels [mid, mid + cin) ARE x (the caller had x's producer write there);
@@ -108,7 +124,7 @@ class ResDetBuilder:
             mid, cin = w1.shape[0], w1.shape[1]
             assert cat.c == mid + cin and x.c == cin
             t = e.conv(x, self._pack(p + ".conv1", [self._bn_part(p + ".conv1", p + ".bn1")], x.c), 1, 0, "relu")
-            e.conv(t, self._pack(p + ".conv2", [self._bn_part(p + ".conv2", p + ".bn2")], t.c), 1, 1, "relu", out=cat.channels(0, mid))
+            self._conv2(p, t, 1, out=cat.channels(0, mid))
             key = (p + ".conv3+downsample", cat.c)
             if key not in self._packed:
                 w3, s3, b3 = self._bn_part(p + ".conv3", p + ".bn3")
@@ -117,7 +133,7 @@ class ResDetBuilder:
                 self._packed[key] = e.pack_conv([(w, torch.ones(w.shape[0]), (b3.double() + bd.double()).float())], cat.c)
             return e.conv(cat, self._packed[key], 1, 0, "relu")
         t = self._rec(p + ".conv1", e.conv(x, self._pack(p + ".conv1", [self._bn_part(p + ".conv1", p + ".bn1")], x.c), 1, 0, "relu"))
-        t = self._rec(p + ".conv2", e.conv(t, self._pack(p + ".conv2", [self._bn_part(p + ".conv2", p + ".bn2")], t.c), stride, 1, "relu"))
+        t = self._rec(p + ".conv2", self._conv2(p, t, stride))
         idn = x
         if p + ".downsample.0.weight" in self.sd:
             idn = e.conv(x, self._pack(p + ".downsample", [self._bn_part(p + ".downsample.0", p + ".downsample.1")], x.c),
@@ -693,6 +709,7 @@ class HipGflDetector(PlanBacked):
     DEFAULTS = dict(start_level=1, num_outs=5, add_extra_convs="on_output", relu_before_extra_convs=False,
                     stacked_convs=4, strides=(8, 16, 32, 64, 128), reg_max=16, depth=50, out_indices=(0, 1, 2, 3),
                     proxies_list=(2, 3, 2, 5, 4, 8, 8, 4, 3, 3), gamma=10.0,
+                    groups=1, base_width=4,  # ResNeXt backbone (groups > 1): checked against the state_dict's conv2 shapes
                     gl_levels=None,          # backbone outputs that get x + Patch_Conv_NonLocal_new(x) (None: those whose
                     gl_assoc="auto")         # neck.gl_fusion.<i>.* keys exist in the state_dict); association of its products
 
@@ -705,6 +722,12 @@ class HipGflDetector(PlanBacked):
         self.kind, self.dtype, self.device, self.autotune = kind, dtype, device, autotune
         self.cfg = dict(self.DEFAULTS, **cfg)
         self.sd = {k: v.detach().cpu() for k, v in state_dict.items()}
+        w1, w2 = self.sd.get("backbone.conv1.weight"), self.sd.get("backbone.layer1.0.conv2.weight")
+        g = self.cfg["groups"]
+        if w1 is not None and w2 is not None and (w2.shape[0] // w2.shape[1] != g or (
+                g > 1 and w2.shape[0] != resnext_width(w1.shape[0], g, self.cfg["base_width"], w1.shape[0]))):
+            raise ValueError("backbone.layer1.0.conv2.weight %s is not that of groups=%d, base_width=%d" %
+                             (tuple(w2.shape), self.cfg["groups"], self.cfg["base_width"]))
         if kind == "gfl":
             self.num_classes = self.sd["bbox_head.gfl_cls.weight"].shape[0]
         else:

@@ -84,7 +84,8 @@ def synth_resdet_state_dict(kind: str, seed: int, x: torch.Tensor, **kw) -> Dict
                 p = "backbone.layer%d.%d" % (i + 1, j)
                 s = 2 if (j == 0 and i > 0) else 1
                 o = torch.relu(bn(p + ".bn1", F.conv2d(t, sd[p + ".conv1.weight"])))
-                o = torch.relu(bn(p + ".bn2", F.conv2d(o, sd[p + ".conv2.weight"], None, s, 1)))
+                w2 = sd[p + ".conv2.weight"]                    # ResNeXt (groups= / base_width= in kw): a grouped conv2
+                o = torch.relu(bn(p + ".bn2", F.conv2d(o, w2, None, s, 1, 1, o.shape[1] // w2.shape[1])))
                 o = bn(p + ".bn3", F.conv2d(o, sd[p + ".conv3.weight"]))
                 idn = t
                 if p + ".downsample.0.weight" in sd:

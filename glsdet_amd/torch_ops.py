@@ -9,6 +9,10 @@ allocated by the op on the input's device, nothing synchronises.  There is no CP
         x NHWC [N,H,W,C] (C % 8 == 0) fp16 or fp32; w = pack_conv_weight(...) ; scale / bias fp32 [cout_pad];
         y NHWC [N,Ho,Wo,ceil8(cout)];  act: 0 none 1 silu 2 relu 3 lrelu 4 gelu 5 sigmoid (| 0x100 residual first)
         reference: BaseConv drone/models/base/baseConv.py:6-19 (+ Bottleneck add, darknet.py:61-62)
+    glsdet::conv2d_grouped(x, w, scale, bias, groups, stride, act) -> y
+        grouped 3x3 conv, pad 1, stride 1 / 2, C = groups * Cg with Cg in 4 / 8 / 16 / 32; w, scale, bias =
+        pack_conv_grouped_weight(...); y NHWC [N,Ho,Wo,C] in x's dtype
+        reference: conv2 of the ResNeXt Bottleneck, ufp/mmdet/models/backbones/resnext.py:55-64
     glsdet::nonlocal_dot(x, tpg, ci, wout, bout) -> y
     glsdet::nonlocal_dot_mfma(x, tpg, ci, wout, bout) -> y     (the same on the matrix cores: ci, C multiples of 32)
         Non_local_Block without its three projections: drone/models/block/non_local/Identity_Conv.py:157-173
@@ -93,6 +97,33 @@ def pack_conv_weight(w: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor, c
     return flat.to(dtype).to(device), sc.to(device), bi.to(device)
 
 
+def grouped_weight_blocks(w: torch.Tensor) -> torch.Tensor:
+    """Grouped 3x3 weights [C, Cg, 3, 3] (C = groups * Cg, Cg in 4 / 8 / 16 / 32) -> the fp32 host image of
+    glsdet_conv2d_grouped's operand: [ceil(C / 32), 9, 32, 32] = [block][tap r*3+s][co_l][ci_l], zero outside the diagonal
+    Cg x Cg blocks and past C (include/glsdet_hip.h)."""
+    C_, cg, R, S = w.shape
+    if (R, S) != (3, 3) or cg not in (4, 8, 16, 32) or C_ % cg:
+        raise ValueError("grouped_weight_blocks: [groups * Cg, Cg, 3, 3] with Cg in 4 / 8 / 16 / 32, got %s" % (tuple(w.shape),))
+    nblk = (C_ + 31) // 32
+    out = torch.zeros(nblk * 32, 9, 32, dtype=torch.float32)          # [co][tap][ci_l]
+    wt = w.detach().float().cpu().permute(0, 2, 3, 1).reshape(C_, 9, cg)
+    co = torch.arange(C_)
+    ci_l = ((co // cg) * cg) % 32                                      # first column of co's group inside its block
+    for j in range(cg):
+        out[co, :, ci_l + j] = wt[:, :, j]
+    return out.reshape(nblk, 32, 9, 32).permute(0, 2, 1, 3).contiguous()
+
+
+def pack_conv_grouped_weight(w: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor, dtype: torch.dtype,
+                             device="cuda") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (grouped_weight_blocks(w) in `dtype`, scale fp32 [ceil32(C)], bias fp32 [ceil32(C)]) on `device`"""
+    blocks = grouped_weight_blocks(w)
+    cpad = blocks.shape[0] * 32
+    sc, bi = torch.ones(cpad), torch.zeros(cpad)
+    sc[:w.shape[0]], bi[:w.shape[0]] = scale.detach().float().cpu(), bias.detach().float().cpu()
+    return blocks.to(dtype).to(device), sc.to(device), bi.to(device)
+
+
 _REGISTERED = False
 
 
@@ -104,6 +135,7 @@ def register():
     lib_def = torch.library.Library("glsdet", "DEF")
     lib_def.define("conv_bn_act(Tensor x, Tensor w, Tensor scale, Tensor bias, int cout, int R, int S, int stride, int pad, "
                    "int act, Tensor? res=None, bool out_fp32=False) -> Tensor")
+    lib_def.define("conv2d_grouped(Tensor x, Tensor w, Tensor scale, Tensor bias, int groups, int stride, int act) -> Tensor")
     lib_def.define("nonlocal_dot(Tensor x, Tensor tpg, int ci, Tensor wout, Tensor bout) -> Tensor")
     lib_def.define("nonlocal_dot_mfma(Tensor x, Tensor tpg, int ci, Tensor wout, Tensor bout) -> Tensor")
     lib_def.define("yolox_decode(Tensor[] levels, int num_classes, int in_h, int in_w, int mode=0, int sigmoid=3) -> Tensor")
@@ -148,6 +180,30 @@ def register():
         n, h, wd, c = x.shape
         ho, wo = (h + 2 * pad - R) // stride + 1, (wd + 2 * pad - S) // stride + 1
         return x.new_empty((n, ho, wo, ceil_to(cout, 8)), dtype=torch.float32 if out_fp32 else x.dtype)
+
+    # ------------------------------------------------------------------ conv2d_grouped
+    def conv2d_grouped(x, w, scale, bias, groups, stride, act):
+        lib = _lib.load()
+        _need_cuda(x, w, scale, bias)
+        n, h, wd, c = x.shape
+        y = torch.empty(n, (h - 1) // stride + 1, (wd - 1) // stride + 1, c, dtype=x.dtype, device=x.device)
+        elems = lib.glsdet_conv_grouped_weight_elems(groups, c // groups if groups > 0 and c % groups == 0 else 0)
+        if elems == 0 or w.dtype != x.dtype or not w.is_contiguous() or w.numel() != elems:
+            raise RuntimeError("conv2d_grouped: w must be pack_conv_grouped_weight(...)'s [ceil(C/32), 9, 32, 32] blocks in x's "
+                               "dtype, C = groups * Cg with Cg in 4 / 8 / 16 / 32")
+        cpad = ceil_to(c, 32)
+        if scale.dtype != torch.float32 or bias.dtype != torch.float32 or scale.numel() < cpad or bias.numel() < cpad:
+            raise RuntimeError("conv2d_grouped: scale / bias must be fp32 [ceil32(C)]")
+        d = ConvDesc()
+        d.x, d.y, d.res = _nhwc_view(x, "conv2d_grouped.x"), _nhwc_view(y, "conv2d_grouped.y"), View()
+        d.w, d.scale, d.bias = w.data_ptr(), scale.data_ptr(), bias.data_ptr()
+        d.R, d.S, d.stride, d.pad, d.act, d.tile_hint = 3, 3, stride, 1, act, 0
+        check(lib.glsdet_conv2d_grouped(C.byref(d), groups, _stream(x)), "conv2d_grouped")
+        return y
+
+    def conv2d_grouped_meta(x, w, scale, bias, groups, stride, act):
+        n, h, wd, c = x.shape
+        return x.new_empty((n, (h - 1) // stride + 1, (wd - 1) // stride + 1, c))
 
     # ------------------------------------------------------------------ nonlocal_dot
     def nonlocal_dot(x, tpg, ci, wout, bout):
@@ -333,7 +389,7 @@ def register():
         same = (got[:, None, :] == rows[None, :, :]).all(-1)                                            # [k, m]
         return torch.argmax(same.to(torch.int8), dim=1)          # first (lowest) index of the identical row
 
-    for name, fn, fm in (("conv_bn_act", conv_bn_act, conv_bn_act_meta), ("nonlocal_dot", nonlocal_dot, lambda x, *a: torch.empty_like(x)),
+    for name, fn, fm in (("conv_bn_act", conv_bn_act, conv_bn_act_meta), ("conv2d_grouped", conv2d_grouped, conv2d_grouped_meta), ("nonlocal_dot", nonlocal_dot, lambda x, *a: torch.empty_like(x)),
                          ("nonlocal_dot_mfma", nonlocal_dot_mfma, lambda x, *a: torch.empty_like(x)),
                          ("yolox_decode", yolox_decode, yolox_decode_meta), ("nms", nms, nms_meta),
                          ("soft_nms", soft_nms, soft_nms_meta), ("ufp_pack", ufp_pack, ufp_pack_meta), ("voc_ap", voc_ap, voc_ap_meta),

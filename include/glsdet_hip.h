@@ -192,6 +192,26 @@ int     glsdet_dwconv2d(const glsdet_conv_desc* d, void* stream);
 /* the same with a dilation (LSKblock.conv_spatial: 7x7, dilation 3, padding 9, groups = dim; drone/models/lsk/LSK.py:31);
  * y extent = floor((x + 2 pad - dilation (k - 1) - 1) / stride) + 1.                                                  */
 int     glsdet_dwconv2d_dilated(const glsdet_conv_desc* d, int32_t dilation, void* stream);
+/* Grouped 3x3 conv + folded BN + act: conv2 of the ResNeXt Bottleneck (ufp/mmdet/models/backbones/resnext.py:55-64,
+ * `groups` = 32 / 64 groups of Cg = 4 / 8 / 16 / 32 channels).  Same descriptor:
+ *     y[n,ho,wo,co] = act( scale[co] * sum_{r,s,j<Cg} x[n, ho*stride-1+r, wo*stride-1+s, (co/Cg)*Cg + j] * weight[co][j][r][s]
+ *                          + bias[co] )
+ * fp32 accumulation in any order, one rounding to y.dtype; out-of-map taps are zeros.  x.c == y.c == groups * Cg (a
+ * multiple of 8), Cg in {4, 8, 16, 32}; R = S = 3, pad = 1, stride 1 or 2; x.dtype == y.dtype (F16 or F32); res empty;
+ * tile_hint 0; x and y may be strided views (y a channel slice of a wider buffer) but must not overlap other than as
+ * disjoint channel slices of one pixel-interleaved buffer.  Anything else: GLSDET_E_ARG (views: their own codes), nothing
+ * launched.
+ *  w      : zero-filled block-diagonal tiles over channel blocks of 32, [ceil(C/32)][9][32][32] elements of x.dtype:
+ *           w[b][r*3+s][co_l][ci_l] = weight[co][ci - (co/Cg)*Cg][r][s] with co = 32 b + co_l, ci = 32 b + ci_l, where
+ *           co < C and ci lies in the group of co; 0 elsewhere.  glsdet_conv_grouped_weight_elems(groups, Cg) elements
+ *           (0 for a group width the kernel refuses).
+ *  scale/bias : fp32 [ceil(C/32) * 32].
+ * On the matrix cores (one K step = one tap of one 32-channel block): 32 / Cg <= 8 times the layer's own multiplies,
+ * where the block-diagonal dense conv over all C channels costs C / Cg times.                                          */
+int     glsdet_conv2d_grouped(const glsdet_conv_desc* d, int32_t groups, void* stream);
+int64_t glsdet_conv_grouped_weight_elems(int32_t groups, int32_t cg);
+/* its time on the device (one kernel: *best_hint = 0), for comparisons by the caller's tuner; synchronises, y is written */
+int     glsdet_conv2d_grouped_tune(const glsdet_conv_desc* d, int32_t groups, void* stream, int32_t* best_hint, float* best_us);
 /* number of ELEMENTS of the packed weight buffer for (cout, R, S, cin, dtype)           */
 int64_t glsdet_conv_weight_elems(int32_t cout, int32_t R, int32_t S, int32_t cin, int32_t dtype);
 int32_t glsdet_conv_kpad(int32_t R, int32_t S, int32_t cin, int32_t dtype);

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """GPU micro-benchmark: every conv kernel variant (tile_hint) on the layer shapes that
-dominate the bench workload.  Prints microseconds and algorithmic TFLOP/s per variant."""
+dominate the bench workload.  Prints microseconds and algorithmic TFLOP/s per variant.
+`grouped`: the grouped 3x3 conv of the ResNeXt backbones against its block-diagonal expansion (grouped_main)."""
 import os
 import sys
 
@@ -61,8 +62,79 @@ HINTS = {"auto": 0, "halo": 2, "halowp": 4, "halo64": 5, "dma64": 6, "dma128": 7
          "ring64g2": 0x208, "ring128g2": 0x209, "ring64k64g2": 0x20a, "ring128k64g2": 0x20b, "ring8k64g2": 0x20d}
 
 
+def _graph_us(eng, launch, reps=20):
+    """microseconds per launch(): `reps` launches recorded into a plan and replayed as ONE hipGraph (an eager python loop is
+    host bound below ~10 us per launch; the figure includes the ~1.5 us boundary between two dependent kernels)"""
+    plan = eng.new_plan()
+    with plan:
+        for _ in range(reps):
+            launch()
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        plan.run(st)
+        st.synchronize()
+        plan.capture(st)
+        plan.launch(st)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(5):
+            plan.launch(st)
+        e1.record(st)
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / (5 * reps)
+
+
+HBM_TBS = 6.3       # achievable HBM rate of the MI355X (float4 copy), TB/s
+
+
+def grouped_shapes(n=8, H=800, W=1344):
+    """the distinct conv2 shapes of X-101-32x4d and 64x4d at n x H x W: per model four stride-1 and three stride-2 layers
+    -> (groups, Cg, n, h, w, stride), h x w = the layer's INPUT map"""
+    out = []
+    for groups in (32, 64):
+        maps = [(H // 4 // 2 ** i, W // 4 // 2 ** i) for i in range(4)]
+        for i, cg in enumerate((4, 8, 16, 32)):
+            if i > 0:
+                out.append((groups, cg, n) + maps[i - 1] + (2,))
+            out.append((groups, cg, n) + maps[i] + (1,))
+    return out
+
+
+def grouped_main(args):
+    """`grouped`: the grouped kernel against the block-diagonal expansion on ITS tuned best variant (the only way to run the
+    layer without the kernel) and the layer's HBM time (input + output + weights at HBM_TBS).  One markdown table row per
+    shape; `small` scales the maps down (a rehearsal)."""
+    import ctypes as C
+    from glsdet_amd.engine import _conv_desc
+    eng = Engine("f16")
+    shapes = grouped_shapes(*((2, 128, 192) if "small" in args else ()))
+    print("| model | conv2 | map | grouped us | expansion us (hint) | HBM us | grouped / HBM | expansion / grouped |")
+    print("|---|---|---|---|---|---|---|---|")
+    for (groups, cg, n, h, w, s) in shapes:
+        c = groups * cg
+        mark = len(eng._keep)
+        x = eng.tensor(n, h, w, c)
+        x.buf.view(torch.float16).normal_()
+        wt = torch.randn(c, cg, 3, 3) / (cg * 9) ** 0.5
+        pk = eng.pack_conv_grouped([(wt, torch.ones(c), torch.zeros(c))], groups)
+        out = eng.conv_grouped(x, pk, s, "relu", expand=False)
+        us_g = _graph_us(eng, lambda: eng.conv_grouped(x, pk, s, "relu", out=out, expand=False))
+        dense = pk.dense()
+        rc, hint, _ = eng._measure(eng.lib.glsdet_conv2d_tune, C.byref(_conv_desc(x, dense, s, 1, "relu", out)))
+        assert rc == 0
+        us_d = _graph_us(eng, lambda: eng.conv(x, dense, s, 1, "relu", out=out, tile_hint=hint), reps=5 if c * h * w > 2e7 else 20)
+        hbm = ((n * h * w + out.n * out.h * out.w) * c * 2 + ((c + 31) // 32) * 9 * 1024 * 2) / (HBM_TBS * 1e6)
+        print("| %dx4d | %dx%d s%d | %dx%d | %.1f | %.1f (%#x) | %.1f | %.2f | %.1f |" %
+              (groups, groups, cg, s, h, w, us_g, us_d, hint, hbm, us_g / hbm, us_d / us_g), flush=True)
+        torch.cuda.synchronize()
+        del eng._keep[mark:], x, out, pk, dense
+        torch.cuda.empty_cache()
+
+
 def main():
     args = sys.argv[1:]
+    if args and args[0] == "grouped":
+        return grouped_main(args[1:])
     use_res = "res" in args
     args = [a for a in args if a != "res"]
     shapes = SHAPES
@@ -94,26 +166,7 @@ def main():
                 res.buf.view(torch.float16).normal_()
             conv = lambda: eng.conv(x, pk, s, (k - 1) // 2, "relu" if use_res else "silu", out=out, tile_hint=h, res=res,
                                     res_first=use_res)
-            # 20 launches recorded into a plan and replayed as ONE hipGraph: an eager python loop is host bound below
-            # ~10 us per launch; the figure includes the ~1.5 us boundary between two dependent kernels
-            reps = 20
-            plan = eng.new_plan()
-            with plan:
-                for _ in range(reps):
-                    conv()
-            st = torch.cuda.Stream()
-            with torch.cuda.stream(st):
-                plan.run(st)
-                st.synchronize()
-                plan.capture(st)
-                plan.launch(st)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(st)
-                for _ in range(5):
-                    plan.launch(st)
-                e1.record(st)
-            torch.cuda.synchronize()
-            us = e0.elapsed_time(e1) * 1e3 / (5 * reps)
+            us = _graph_us(eng, conv)
             line += "%s %.1fus %.0fTF | " % (name, us, flops / us / 1e6)
         print(line, flush=True)
 
