@@ -39,6 +39,24 @@ enum { GLSDET_ACT_NONE = 0, GLSDET_ACT_SILU = 1, GLSDET_ACT_RELU = 2, GLSDET_ACT
         * resnet.py:292-301).  Without the flag the order is act(conv*scale+bias) + res
         * (YOLOX Bottleneck, drone/models/base/darknet.py:61-63).                            */
        GLSDET_ACT_RES_FIRST = 0x100 };
+/* Accuracy of the activation epilogues (tests/act_reference.py derives each bound, tests/test_act_exact.py enforces it on
+ * every kernel variant).  v = the fp32 pre-activation conv*scale+bias (+ res with GLSDET_ACT_RES_FIRST), y the float64
+ * value of the activation at v, u = 2^-24.  The result is the rounding (nearest even; fp16 overflows to inf) to the output
+ * type of a value within tol of y:
+ *     NONE, RELU   tol = 0 (the one rounding to the output type)
+ *     LRELU        v > 0 ? v : 0.1f * v.  F32: exactly float(0.1f * v); F16: tol = u |y| (the fp32 product, rounded again)
+ *     SILU         F16: v * rcp(1 + exp2(v * -log2e)), v_exp_f32 / v_rcp_f32:  tol = (8 + 2 |v| sigmoid(-v)) u |y| + 2^-120
+ *                  F32, and glsdet_dwconv2d in both dtypes: v / (1 + expf(-v)):  tol = 6 u |y| + 2^-120
+ *     SIGMOID      1 / (1 + expf(-v)).  F32: tol = 6 u |y| + 2^-120; F16: tol = 4 u (|y| + |v| / 2)
+ *     GELU         0.5f * v * (1 + erff(v * 0.70710678f)): tol = 4 u (|y| + |v| / 2) -- 1 + erff cancels for negative v
+ * With a residual added after the activation one more fp32 rounding of the sum: tol + u |y + res|.  An fp16 output with a
+ * residual is rounded ONCE, from the fp32 sum.  Every kernel variant (tile_hint) gives the same bits for the same problem,
+ * and the vector epilogue (no residual) the same bits as the scalar one (GLSDET_ACT_RES_FIRST), zeros compared as zeros.
+ * Special values: +-0 keep their sign through NONE, LRELU, SILU and GELU; a NaN pre-activation gives NaN EXCEPT under RELU,
+ * where relu(NaN) = 0 (fmaxf / v_max semantics; torch.relu gives NaN); +inf gives +inf (SIGMOID: 1); -inf gives -inf under
+ * NONE and LRELU, 0 under RELU and SIGMOID, and NaN under SILU and GELU (-inf * 0).
+ * glsdet_dwconv2d / glsdet_dwconv2d_dilated accept NONE, SILU, RELU and LRELU only; glsdet_csp_fused SILU only;
+ * glsdet_resnet_stem_pool has RELU compiled in; every other entry point with an `act` takes all six codes. */
 enum {
   GLSDET_OK = 0,
   GLSDET_E_ARG = -1,      /* inconsistent shapes / unsupported parameter            */
@@ -98,7 +116,9 @@ typedef struct glsdet_conv_desc {
                             *            pixel tiles (h = 13: 10 x 24 resp. 6 x 42) instead of 8 x 16 (8 x 32) -- fewer
                             *            wasted lanes on 50 x 84 / 25 x 42 maps
                             *   variant  16 + v, v = 0..15: row v of the table in csrc/conv_gemm.hip (tile, ring depth,
-                            *            K panel, weight-resident, single shot)
+                            *            K panel, weight-resident, single shot); variant 19 (128 x 128 tile, three stages of
+                            *            128-byte panels) takes no residual with an fp32 output: ring + fp32 residual tile
+                            *            exceed the 160 KiB of LDS
                             *   tile     co << 16 | px: the generic kernel on a co x px tile -- 128x128, 64x128, 32x128,
                             *            64x64, and 128 << 16 | 0 = the 8-wave 128 x 256 tile (Cin a whole number of K
                             *            steps, no chained conv); glsdet_conv2d_multi has 128x128, 64x128, 64x64 only
@@ -187,7 +207,8 @@ int     glsdet_csp_fused(const glsdet_csp_desc* d, int32_t hint, void* stream);
 int     glsdet_csp_fused_tune(const glsdet_csp_desc* d, void* stream, int32_t* best_hint, float* best_us);
 /* Depthwise k x k conv + folded BN + act (`dconv` of DWConv, drone/models/base/baseConv.py:22-30;
  * mmcv DepthwiseSeparableConvModule).  Same descriptor; x.c == y.c; w = [R*S][x.c] elements of
- * x.dtype (tap-major), scale/bias fp32 [x.c]; res must be empty. */
+ * x.dtype (tap-major), scale/bias fp32 [x.c]; res must be empty; act: GLSDET_ACT_NONE / SILU / RELU / LRELU (codes 0..3;
+ * GELU, SIGMOID and GLSDET_ACT_RES_FIRST are refused with GLSDET_E_ARG before anything is launched). */
 int     glsdet_dwconv2d(const glsdet_conv_desc* d, void* stream);
 /* the same with a dilation (LSKblock.conv_spatial: 7x7, dilation 3, padding 9, groups = dim; drone/models/lsk/LSK.py:31);
  * y extent = floor((x + 2 pad - dilation (k - 1) - 1) / stride) + 1.                                                  */

@@ -110,3 +110,22 @@ def test_new_entry_points_validate_their_operands_on_the_host():
     m = (C.c_double * 3)(0.5, 0.5, 0.5)
     assert lib.glsdet_pil_resize_normalize(0x1000, 10, 10, 0x2000, 0x3000, 5, 64, 0x2000, 0x3000, 5, 64, 0x4000, 0x5000,
                                            32, 32, 0, 0, m, m, None) < 0 and "does not fit" in _err(lib)
+
+
+def test_dwconv_refuses_the_activations_its_kernel_does_not_implement():
+    """dwconv.hip's epilogue lists SiLU, ReLU and LReLU and would apply NO activation for any other code: the entry point
+    must refuse codes 4 (GELU), 5 (sigmoid), unknown ones and the RES_FIRST flag -- after every other operand has passed, and
+    before anything is launched (the act check of glsdet_dwconv2d_dilated precedes the launch; no valid call is made here:
+    the pointers are never dereferenced)"""
+    import ctypes as C
+    from glsdet_amd import _lib
+    lib = _lib.load()
+    for dtype in (0, 1):
+        d = _lib.ConvDesc()
+        d.x, d.y = _view(1, 8, 10, 16, dtype), _view(1, 8, 10, 16, dtype, base=0x40000)
+        d.w, d.scale, d.bias = 0x80000, 0x90000, 0xA0000
+        d.R, d.S, d.stride, d.pad, d.tile_hint = 3, 3, 1, 1, 0
+        for act in (4, 5, 6, -1, 0x101, 0x102):
+            d.act = act
+            assert lib.glsdet_dwconv2d(C.byref(d), None) < 0 and "dwconv2d: bad act" in _err(lib), (dtype, act)
+            assert lib.glsdet_dwconv2d_dilated(C.byref(d), 1, None) < 0 and "dwconv2d: bad act" in _err(lib), (dtype, act)
