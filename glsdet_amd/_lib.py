@@ -103,6 +103,11 @@ _SIGS = {
     "glsdet_nonlocal_mfma_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "glsdet_nonlocal_mfma": (C.c_int, [C.POINTER(View), C.POINTER(View), C.c_int32, C.c_int32, C.POINTER(C.c_void_p),
                                        C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.POINTER(View), C.c_void_p]),
+    "glsdet_lvc_encode_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "glsdet_lvc_encode": (C.c_int, [C.POINTER(View), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "glsdet_lvc_gate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    "glsdet_channel_fuse": (C.c_int, [C.POINTER(View), C.POINTER(View), C.POINTER(View), C.c_void_p, C.c_int32, C.c_void_p]),
     "glsdet_attn_split": (C.c_int, [C.POINTER(View), C.c_void_p, C.c_void_p]),
     "glsdet_nonlocal_split": (C.c_int, [C.POINTER(View), C.POINTER(View), C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                         C.c_void_p, C.POINTER(View), C.c_void_p, C.c_int32, C.c_void_p]),

@@ -14,7 +14,7 @@ from typing import Tuple
 # drone/models/base/yolox.py:240-241
 DEPTH = {"nano": 0.33, "tiny": 0.33, "s": 0.33, "m": 0.67, "l": 1.00, "x": 1.33}
 WIDTH = {"nano": 0.25, "tiny": 0.375, "s": 0.50, "m": 0.75, "l": 1.00, "x": 1.25}
-KINDS = ("base", "gl", "cross", "cross10")
+KINDS = ("base", "gl", "cross", "cross10", "cfp")
 
 
 class _Table(OrderedDict):
@@ -101,6 +101,41 @@ class _Table(OrderedDict):
         self.plain(p + ".channel_conv", 2 * mid, cout, 1)
 
 
+def evc_table(t: "_Table", p: str, c: int):
+    """EVCBlock(c, c) (drone/models/cfp/evc_blocks.py:281-297) in the registration order of its __init__s: a module's own
+    parameters precede its children's (LightMLPBlock's layer scales come first), BatchNorm1d(64) is per code, and
+    l_MLP.linear is registered but never used by the forward."""
+    t[p + ".conv1.weight"] = (c, c, 7, 7)
+    _bn(t, p + ".bn1", c)
+    q = p + ".lvc.conv_1"                   # ConvBlock (cfp/Functions.py:88-114), res_conv=True
+    for name, cin, cout, k in (("conv1", c, c // 4, 1), ("conv2", c // 4, c // 4, 3), ("conv3", c // 4, c, 1)):
+        t["%s.%s.weight" % (q, name)] = (cout, cin, k, k)
+        _bn(t, "%s.bn%s" % (q, name[-1]), cout)
+    t[q + ".residual_conv.weight"] = (c, c, 1, 1)
+    _bn(t, q + ".residual_bn", c)
+    q = p + ".lvc.LVC"                      # evc_blocks.py:223-230
+    t[q + ".0.weight"] = (c, c, 1, 1)
+    _bn(t, q + ".1", c)
+    t[q + ".3.codewords"] = (64, c)
+    t[q + ".3.scale"] = (64,)
+    _bn(t, q + ".4", 64)
+    t[p + ".lvc.fc.0.weight"] = (c, c)
+    t[p + ".lvc.fc.0.bias"] = (c,)
+    q = p + ".l_MLP"                        # evc_blocks.py:244-268
+    t[q + ".layer_scale_1"] = (c,)
+    t[q + ".layer_scale_2"] = (c,)
+    t.conv_bn(q + ".dw.dconv", c, c, 1, groups=c)
+    t.conv_bn(q + ".dw.pconv", c, c, 1)
+    t[q + ".linear.weight"] = (c, c)
+    t[q + ".linear.bias"] = (c,)
+    for name in ("norm1", "norm2"):
+        t["%s.%s.weight" % (q, name)] = (c,)
+        t["%s.%s.bias" % (q, name)] = (c,)
+    t.plain(q + ".mlp.fc1", c, 4 * c, 1)
+    t.plain(q + ".mlp.fc2", 4 * c, c, 1)
+    t.plain(p + ".cnv1", 2 * c, c, 1)
+
+
 def cross_head_table(t: "_Table", h: str, num_classes: int, wid: float, dw: bool):
     """Cross-scale decoupled head, drone/models/lsk/yolox6.py:7-67 (= new/yolox6.py)."""
     c = [int(256 * wid), int(512 * wid), int(1024 * wid)]
@@ -153,6 +188,8 @@ def state_dict_shapes(kind: str, phi: str, num_classes: int,
         t.plain(b + ".P4_Identity.conv", c[1], c[1], 5)
     t.any_conv(b + ".bu_conv1", c[1], c[1], 3, dw)
     t.csp(b + ".C3_n4", 2 * c[1], c[2], n, dw)
+    if kind == "cfp":                       # cfp/yolox_cfp.py:123: EVCBlock(int(512 * width), int(512 * width))
+        evc_table(t, b + ".evcblock", c[1])
     if kind == "cross10":                   # new/yolox10.py:236-255: Patch_Conv_NonLocal_new(C, C, channel_scale=1) on dark3 / 4 / 5
         for i in range(3):
             gl_fusion_table(t, "%s.Patch_conv_feat%d" % (b, i + 1), c[i], "non_linear")

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnArgs a) {
   const int N = S.H * W;
   const int pbeg = z * S.chunk, pend = min(N, pbeg + S.chunk);
   double sum = 0.0, sq = 0.0;
-  for (int p = pbeg + r0; p < pend; p += rows) {
+  for (int p = r0 < rows ? pbeg + r0 : pend; p < pend; p += rows) {      // (threads past rows * vcols own no column)
     const V v = *reinterpret_cast<const V*>(S.x + (b * S.xsn + (p / W) * S.xsh + (p % W) * S.xsw + cc * VN) * (long)sizeof(T));
 #pragma unroll
     for (int e = 0; e < VN; ++e) {
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GnArgs a) {
     sc[e] = (float)ga;
     sh[e] = (float)((double)S.beta[cc * VN + e] - s_mean[g] * ga);
   }
-  for (int p = blockIdx.x * rows + r0; p < N; p += S.gb * rows) {
+  for (int p = r0 < rows ? blockIdx.x * rows + r0 : N; p < N; p += S.gb * rows) {
     const long ox = (b * S.xsn + (p / W) * S.xsh + (p % W) * S.xsw + cc * VN) * (long)sizeof(T);
     const long oy = (b * S.ysn + (p / W) * S.ysh + (p % W) * S.ysw + cc * VN) * (long)sizeof(T);
     V v = *reinterpret_cast<const V*>(S.x + ox);
@@ -398,8 +398,10 @@ static int groupnorm_sets(const glsdet_view* x, const glsdet_view* y, int32_t n_
   if ((uintptr_t)stats & 7) GLS_FAIL(GLSDET_E_ALIGN, "groupnorm: stats must be 8-byte aligned");
   const int dt = x[0].dtype, C = x[0].c, nimg = x[0].n;
   const int vn = 16 / dtype_size(dt);
-  if (groups < 1 || groups > 256 || C % groups || (C / groups) % vn || C / vn > 256 || 256 % (C / vn))
-    GLS_FAIL(GLSDET_E_ARG, "groupnorm: need C %% groups == 0, (C/groups) %% %d == 0 and C/%d a divisor of 256 (C=%d groups=%d)",
+  // C / vn a divisor of 256: every thread of a workgroup owns a vector column.  Multiples of 32 channels up to 256 vectors
+  // (GroupNorm(1, C) of the EVC block at C = 192 / 384) are taken too: the threads past rows * vcols then idle.
+  if (groups < 1 || groups > 256 || C % groups || (C / groups) % vn || C / vn > 256 || (256 % (C / vn) && C % 32))
+    GLS_FAIL(GLSDET_E_ARG, "groupnorm: need C %% groups == 0, (C/groups) %% %d == 0 and C/%d a divisor of 256 or C %% 32 == 0 (C=%d groups=%d)",
              vn, vn, C, groups);
   GnArgs a = {};
   a.n = n_sets; a.C = C; a.groups = groups; a.act = act; a.eps = eps;

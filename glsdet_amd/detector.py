@@ -18,7 +18,8 @@ class _Compiled:
 
 class HipDetector(PlanBacked):
     """kind: 'base' (YOLOX) | 'gl' (YOLOX + GL-fusion neck) | 'cross' (cross-scale head, new/yolox6.py) | 'cross10' (the
-    same behind residual Patch_Conv_NonLocal_new blocks on dark3 / 4 / 5, new/yolox10.py).  state_dict uses the
+    same behind residual Patch_Conv_NonLocal_new blocks on dark3 / 4 / 5, new/yolox10.py) | 'cfp' (YOLOX with the EVCBlock
+    on the upsampled P5 lateral, cfp/yolox_cfp.py).  state_dict uses the
     reference's key names (drone flavour).  dtype 'f16' (fp16 storage / fp32 accumulate,
     the benchmarked mode) or 'f32' (exact-f32 MFMA, the strict-parity mode)."""
 

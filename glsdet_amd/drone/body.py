@@ -58,8 +58,17 @@ class TableModule(nn.Module):
                 self.register_parameter(flat, nn.Parameter(torch.ones(shape), requires_grad=False))
             elif key.endswith("bias"):
                 self.register_parameter(flat, nn.Parameter(torch.zeros(shape), requires_grad=False))
-            else:       # conv weights: torch's default kaiming-uniform(a=sqrt(5)) bound
-                fan_in = shape[1] * shape[2] * shape[3]
+            elif key.endswith("codewords"):                               # Encoding (cfp/Functions.py:31-36)
+                std = 1.0 / (shape[0] * shape[1]) ** 0.5
+                self.register_parameter(flat, nn.Parameter(torch.empty(shape).uniform_(-std, std), requires_grad=False))
+            elif key.endswith(".scale"):
+                self.register_parameter(flat, nn.Parameter(torch.empty(shape).uniform_(-1, 0), requires_grad=False))
+            elif ".layer_scale_" in key:                                  # LightMLPBlock (cfp/evc_blocks.py:265-268)
+                self.register_parameter(flat, nn.Parameter(1e-5 * torch.ones(shape), requires_grad=False))
+            else:       # conv / linear weights: torch's default kaiming-uniform(a=sqrt(5)) bound
+                fan_in = 1
+                for v in shape[1:]:
+                    fan_in *= v
                 bound = 1.0 / fan_in ** 0.5
                 self.register_parameter(flat, nn.Parameter(torch.empty(shape).uniform_(-bound, bound),
                                                            requires_grad=False))
@@ -149,3 +158,10 @@ class Cross10YoloBody(CrossYoloBody):
     PAFPN (:236-266), then the cross-scale head.  Its import of `models.decouple.darknet` is missing from the reference
     checkout; new/darknet.py has the same classes and exposes dark2."""
     kind = "cross10"
+
+
+class CfpYoloBody(HipYoloBody):
+    """drone/models/cfp/yolox_cfp.py, the "centralized feature pyramid": the plain YOLOX whose top-down path sends the
+    upsampled P5 lateral through an EVCBlock (cfp/evc_blocks.py:281-308) before the first concat.  The reference file needs
+    `timm` for imports only; nothing of it runs at drop_path = 0."""
+    kind = "cfp"

@@ -900,6 +900,35 @@ class Engine:
               "nonlocal_multi")
         return outs
 
+    # ---- EVC block (csrc/evc.hip)
+    def lvc_encode(self, x: TView, codewords: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+        """glsdet_lvc_encode: the codebook encoding of every image of x -> fp32 [n, 64, C]; codewords fp32 [64, C] and
+        scale fp32 [64] on the device.  Workspace and result are allocated here, i.e. once, at plan build."""
+        assert codewords.dtype == torch.float32 and tuple(codewords.shape) == (64, x.c) and scale.numel() == 64
+        nbytes = self.lib.glsdet_lvc_encode_workspace_bytes(x.n, x.h, x.w, x.c)
+        ws = self.raw(nbytes)
+        E = self.raw(x.n * 64 * x.c * 4)[: x.n * 64 * x.c * 4].view(torch.float32).view(x.n, 64, x.c)
+        check(self.lib.glsdet_lvc_encode(C.byref(x.as_c()), codewords.data_ptr(), scale.data_ptr(), ws.data_ptr(), nbytes,
+                                         E.data_ptr(), _stream_ptr(self.stream)), "lvc_encode")
+        return E
+
+    def lvc_gate(self, E: torch.Tensor, n: int, c: int, a: torch.Tensor, b: torch.Tensor, fc_w: torch.Tensor,
+                 fc_b: torch.Tensor) -> torch.Tensor:
+        """glsdet_lvc_gate -> gam fp32 [n, C]"""
+        assert tuple(E.shape) == (n, 64, c) and tuple(fc_w.shape) == (c, c) and a.numel() == 64 and b.numel() == 64
+        gam = self.raw(n * c * 4)[: n * c * 4].view(torch.float32).view(n, c)
+        check(self.lib.glsdet_lvc_gate(E.data_ptr(), n, c, a.data_ptr(), b.data_ptr(), fc_w.data_ptr(), fc_b.data_ptr(),
+                                       gam.data_ptr(), _stream_ptr(self.stream)), "lvc_gate")
+        return gam
+
+    def channel_fuse(self, a: TView, t: Optional[TView], v: torch.Tensor, mode: int, out: Optional[TView] = None) -> TView:
+        """glsdet_channel_fuse: mode 0 relu(a + a * v[n, c]), mode 1 a + v[c] * t"""
+        if out is None:
+            out = self.tensor(a.n, a.h, a.w, a.c, a.dtype)
+        check(self.lib.glsdet_channel_fuse(C.byref(a.as_c()), C.byref(t.as_c()) if t is not None else None, C.byref(out.as_c()),
+                                           v.data_ptr(), mode, _stream_ptr(self.stream)), "channel_fuse")
+        return out
+
     # ---- Patch_Conv_NonLocal_adapt_new: device-side quadrant split
     def attn_split(self, att: TView) -> torch.Tensor:
         """-> device int32[4] {row split, column split above it, column split from it on, 0} (glsdet_attn_split)."""

@@ -31,11 +31,23 @@ from .engine import Engine, TView, ceil_to, fold_bn
 BN_EPS = 1e-3   # drone/models/base/baseConv.py:12
 
 
+def cfp_bn_eps(prefix: str) -> float:
+    """BatchNorm eps of kind `cfp` by region: cfp/yolox_cfp.py:9 takes BaseConv / CSPLayer / DWConv from cfp/evc_blocks.py,
+    whose BaseConv is nn.BatchNorm2d(out_channels) with torch's default eps, for the whole neck and head; only the
+    CSPDarknet (`backbone.backbone.*`) keeps base/baseConv.py's 1e-3.  ConvBlock (cfp/Functions.py:90) has 1e-6."""
+    if prefix.startswith("backbone.backbone."):
+        return BN_EPS
+    if ".lvc.conv_1." in prefix:
+        return 1e-6
+    return 1e-5
+
+
 class NetBuilder:
     def __init__(self, eng: Engine, sd: Dict[str, torch.Tensor]):
         self.e = eng
         self.sd = {k: v.detach().cpu() for k, v in sd.items()}
         self._packed = {}
+        self.bn_eps = lambda prefix: BN_EPS     # eps of the BatchNorm folded at `prefix` (kind cfp: cfp_bn_eps)
         self._override = {}     # BaseConv name -> (w, scale, bias) replacing the state_dict's (compose_1x1_input)
         self.trace = None       # tests: dict name -> NCHW fp32 snapshot of every stored tensor (eager emission only)
         self.composed = None    # tests: dict filled with name -> (w, scale, bias) of every host-composed conv; when set, a
@@ -53,7 +65,7 @@ class NetBuilder:
         if p in self._override:            # a BaseConv whose weights were composed with the linear conv in front of it
             return self._override[p]
         s, b = fold_bn(self.sd[p + ".bn.weight"], self.sd[p + ".bn.bias"],
-                       self.sd[p + ".bn.running_mean"], self.sd[p + ".bn.running_var"], BN_EPS)
+                       self.sd[p + ".bn.running_mean"], self.sd[p + ".bn.running_var"], self.bn_eps(p))
         return self.sd[p + ".conv.weight"], s, b
 
     def _plain_part(self, p: str):
@@ -680,14 +692,91 @@ class NetBuilder:
         self._rec(stem, y, 0, w.shape[0])
         return y
 
+    # ------------------------------------------------------------------ EVC block (kind cfp)
+    def _bn_conv(self, conv: str, bn: str, x: TView, pad: int, act: str, res: Optional[TView] = None,
+                 res_first: bool = False) -> TView:
+        """nn.Conv2d(bias=False) at `conv` + BatchNorm2d at `bn` (separately named, as in ConvBlock / EVCBlock) + act"""
+        if conv not in self._packed:
+            s, b = fold_bn(self.sd[bn + ".weight"], self.sd[bn + ".bias"], self.sd[bn + ".running_mean"],
+                           self.sd[bn + ".running_var"], self.bn_eps(bn))
+            self._packed[conv] = self.e.pack_conv([(self.sd[conv + ".weight"], s, b)], x.c)
+        y = self.e.conv(x, self._packed[conv], 1, pad, act, res=res, res_first=res_first)
+        self._rec(conv, y, 0, self._packed[conv][3])
+        return y
+
+    def _f32(self, key: str, make=None) -> torch.Tensor:
+        """a state_dict vector (or make()) as a resident fp32 device tensor"""
+        if ("f32", key) not in self._packed:
+            self._packed[("f32", key)] = self.e.upload((self.sd[key] if make is None else make()).float())
+        return self._packed[("f32", key)]
+
+    def lvc(self, p: str, x: TView, out: Optional[TView] = None) -> TView:
+        """LVCBlock.forward (cfp/evc_blocks.py:233-240): ConvBlock with its residual 1x1 in the last conv's epilogue
+        (GLSDET_ACT_RES_FIRST), the encoding's 1x1 + BN + ReLU, glsdet_lvc_encode, glsdet_lvc_gate, relu(x + x * gam)."""
+        e, q = self.e, p + ".conv_1"
+        r = self._bn_conv(q + ".residual_conv", q + ".residual_bn", x, 0, "none")
+        t = self._bn_conv(q + ".conv1", q + ".bn1", x, 0, "relu")
+        t = self._bn_conv(q + ".conv2", q + ".bn2", t, 1, "relu")
+        t = self._bn_conv(q + ".conv3", q + ".bn3", t, 0, "relu", res=r, res_first=True)
+        z = self._bn_conv(p + ".LVC.0", p + ".LVC.1", t, 0, "relu")
+        E = e.lvc_encode(z, self._f32(p + ".LVC.3.codewords"), self._f32(p + ".LVC.3.scale"))
+        bn = p + ".LVC.4"                       # BatchNorm1d(64) on [B, 64, C]: statistics and affine per CODE, eps 1e-5
+        ab = lambda i: fold_bn(self.sd[bn + ".weight"], self.sd[bn + ".bias"], self.sd[bn + ".running_mean"],
+                               self.sd[bn + ".running_var"], self.bn_eps(bn))[i]
+        gam = e.lvc_gate(E, x.n, x.c, self._f32(bn + ".a", lambda: ab(0)), self._f32(bn + ".b", lambda: ab(1)),
+                         self._f32(p + ".fc.0.weight"), self._f32(p + ".fc.0.bias"))
+        if self.trace is not None:
+            self.trace[p + ".encoding"] = E.cpu().clone()
+            self.trace[p + ".gam"] = gam.cpu().clone()
+        y = e.channel_fuse(t, None, gam, 0, out=out)
+        self._rec(p, y, 0, x.c)
+        return y
+
+    def light_mlp(self, p: str, x: TView, out: Optional[TView] = None) -> TView:
+        """LightMLPBlock.forward (cfp/evc_blocks.py:270-277): x + ls1 * dw(GN(x)), then + ls2 * mlp(GN(.)).  The second
+        layer scale rides in the fp32 scale / bias vectors of mlp.fc2's epilogue with the shortcut as its residual: folded
+        into fp16 weights it would underflow at the reference's initial 1e-5.  l_MLP.linear is never used."""
+        e, c = self.e, x.c
+        g1 = e.groupnorm(x, 1, self._f32(p + ".norm1.weight"), self._f32(p + ".norm1.bias"), 1e-5, "none",
+                         out=e.tensor(x.n, x.h, x.w, c))
+        d = self._dw_separable([p + ".dw"], g1, 1, "silu", None, None)
+        y1 = e.channel_fuse(x, d, self._f32(p + ".layer_scale_1"), 1)
+        self._rec(p + ".y1", y1, 0, c)
+        g2 = e.groupnorm(y1, 1, self._f32(p + ".norm2.weight"), self._f32(p + ".norm2.bias"), 1e-5, "none",
+                         out=e.tensor(x.n, x.h, x.w, c))
+        h = self.plain(p + ".mlp.fc1", g2, act="gelu")
+        key = p + ".mlp.fc2*ls2"
+        if key not in self._packed:
+            ls = self.sd[p + ".layer_scale_2"].double()
+            self._packed[key] = e.pack_conv([(self.sd[p + ".mlp.fc2.weight"], ls.float(),
+                                              (ls * self.sd[p + ".mlp.fc2.bias"].double()).float())], h.c)
+        y = e.conv(h, self._packed[key], 1, 0, "none", out=out, res=y1)
+        self._rec(p, y, 0, c)
+        return y
+
+    def evc(self, p: str, x: TView, out: Optional[TView] = None) -> TView:
+        """EVCBlock.forward (cfp/evc_blocks.py:299-308), in == out channels: 7x7 conv + BN + ReLU, 3x3 stride-1 max pool,
+        then cnv1 over [lvc | l_MLP], the two branches writing the channel halves of one buffer."""
+        e, c = self.e, x.c
+        t = self._bn_conv(p + ".conv1", p + ".bn1", x, 3, "relu")
+        x1 = e.pool2d(t, 3, 1, 1)
+        self._rec(p + ".maxpool", x1, 0, c)
+        cat = e.tensor(x.n, x.h, x.w, 2 * c)
+        self.lvc(p + ".lvc", x1, out=cat.channels(0, c))
+        self.light_mlp(p + ".l_MLP", x1, out=cat.channels(c, 2 * c))
+        return self.plain(p + ".cnv1", cat, out=out)
+
     # ------------------------------------------------------------------ necks
-    def pafpn(self, p: str, img: torch.Tensor, gl: bool, fold_p5: bool = False, residual_gl: bool = False) -> List[TView]:
+    def pafpn(self, p: str, img: torch.Tensor, gl: bool, fold_p5: bool = False, residual_gl: bool = False,
+              evc: bool = False) -> List[TView]:
         """YOLOPAFPN (base/yolox.py:170-234) or its GL-fusion variant
         (block/non_local/yolo_patch_nonlocal_plus.py:180-247) when gl=True.  fold_p5: the caller's head is yolox_head,
         which may take P5_Identity into its stem (stem_of_identity); the third output is then C3_n4's.
         residual_gl (new/yolox10.py:236-266): the neck reads feat_i + Patch_Conv_NonLocal_new(feat_i) in place of dark3 /
         dark4 / dark5.  The backbone then writes the three maps to buffers of their own and the sums land where feat1 /
-        feat2 live otherwise (the concat slices); the third goes to the tensor lateral_conv0 reads."""
+        feat2 live otherwise (the concat slices); the third goes to the tensor lateral_conv0 reads.
+        evc (cfp/yolox_cfp.py:183-186): the upsampled P5 lateral goes through the EVCBlock `p.evcblock`, whose last conv
+        writes the concat slice the upsample writes otherwise."""
         sd = self.sd
         c3 = self.conv_out_channels(p + ".backbone.dark3.1.conv3")
         c4 = self.conv_out_channels(p + ".backbone.dark4.1.conv3")
@@ -722,7 +811,10 @@ class NetBuilder:
                 self.patch_conv(pc1, feat1, 2, True, out=cat_p4.channels(2 * c4, 3 * c4))
             self.patch_conv(p + ".Patch_conv_feat2", feat2, 1, False, out=cat_n3.channels(2 * c3, 3 * c3))
         P5 = self.cba(p + ".lateral_conv0", feat3, out=cat_n4.channels(c4, 2 * c4))
-        e.resample(P5, 2, out=cat_p4.channels(0, c4))
+        if evc:
+            self.evc(p + ".evcblock", e.resample(P5, 2), out=cat_p4.channels(0, c4))
+        else:
+            e.resample(P5, 2, out=cat_p4.channels(0, c4))
         t = self.csp(p + ".C3_p4", cat_p4, False)
         P4 = self.cba(p + ".reduce_conv1", t, out=cat_n3.channels(c3, 2 * c3))
         e.resample(P4, 2, out=cat_p3.channels(0, c3))
@@ -823,16 +915,18 @@ class NetBuilder:
 
 
 def build_forward(kind: str, eng: Engine, sd, img: torch.Tensor, trace: Optional[dict] = None, composed: Optional[dict] = None):
-    """Emit the whole raw forward of a `kind` in {'base','gl','cross','cross10'} detector for the static input
+    """Emit the whole raw forward of a `kind` in {'base','gl','cross','cross10','cfp'} detector for the static input
     tensor `img` (NCHW fp32 on the device).  Returns (list of fp32 level views, num_classes).
     trace: dict filled with a snapshot of every stored tensor (eager emission only; parity tests).  composed: dict filled
     with the host-composed convs' (w, scale, bias); a trace then keeps the composed forms the benchmark runs."""
     b = NetBuilder(eng, sd)
     b.trace, b.composed = trace, composed
-    if kind not in ("base", "gl", "cross", "cross10"):
+    if kind not in ("base", "gl", "cross", "cross10", "cfp"):
         raise ValueError("unknown detector kind %r" % kind)
+    if kind == "cfp":
+        b.bn_eps = cfp_bn_eps
     fold = kind == "gl" and not b.is_depthwise("head.stems.2")
-    feats = b.pafpn("backbone", img, gl=(kind == "gl"), fold_p5=fold, residual_gl=(kind == "cross10"))
+    feats = b.pafpn("backbone", img, gl=(kind == "gl"), fold_p5=fold, residual_gl=(kind == "cross10"), evc=(kind == "cfp"))
     if kind in ("cross", "cross10"):
         outs = b.cross_scale_head("head", [b.features["dark2"]] + feats)
     else:

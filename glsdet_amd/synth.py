@@ -18,6 +18,10 @@ def synth_tensor(key: str, shape: Tuple[int, ...], seed: int) -> np.ndarray:
     leaf = key.rsplit(".", 1)[-1]
     if leaf == "num_batches_tracked":
         return np.zeros(shape, np.int64)
+    if leaf == "codewords":                              # Encoding (cfp/Functions.py:33-34): order 0.3, so that the codes differ
+        return (0.3 * rng.standard_normal(shape)).astype(np.float32)
+    if leaf.startswith("layer_scale_"):                  # LightMLPBlock (cfp/evc_blocks.py:265-268): order 1, not the init's 1e-5
+        return rng.uniform(0.5, 1.5, shape).astype(np.float32)
     if leaf == "scale":                                  # mmcv Scale (gfl_head.py:151)
         return rng.uniform(0.7, 1.3, shape).astype(np.float32)
     if leaf in ("proxies", "_embedding"):               # mp_head.py:78-91

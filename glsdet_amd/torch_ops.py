@@ -16,6 +16,13 @@ allocated by the op on the input's device, nothing synchronises.  There is no CP
     glsdet::nonlocal_dot(x, tpg, ci, wout, bout) -> y
     glsdet::nonlocal_dot_mfma(x, tpg, ci, wout, bout) -> y     (the same on the matrix cores: ci, C multiples of 32)
         Non_local_Block without its three projections: drone/models/block/non_local/Identity_Conv.py:157-173
+    glsdet::lvc_encode(x, codewords, scale) -> E fp32 [N, 64, C]
+        the codebook Encoding layer, drone/models/cfp/Functions.py:25-84: x NHWC (C a multiple of 32, at most 640),
+        codewords fp32 [64, C], scale fp32 [64]
+    glsdet::lvc_gate(E, a, b, fc_w, fc_b) -> gam fp32 [N, C]
+        BatchNorm1d per code (folded: a, b fp32 [64]) + ReLU + mean over the codes + fc + sigmoid, cfp/evc_blocks.py:223-238
+    glsdet::channel_fuse(a, t, v, mode) -> y
+        mode 0: relu(a + a * v[n, c]) (evc_blocks.py:239; t = None); mode 1: a + v[c] * t (evc_blocks.py:272)
     glsdet::yolox_decode(levels, num_classes, in_h, in_w, mode=0, sigmoid=3) -> pred [N, A, 5+nc]
         decode_outputs, drone/models/core/utils_bbox.py:254-306 (mode 1: mmdet YOLOXHead._bbox_decode); sigmoid: bit 0
         objectness, bit 1 classes, channels outside the mask stay raw logits (the variants of utils_bbox.py:36-253)
@@ -138,6 +145,9 @@ def register():
     lib_def.define("conv2d_grouped(Tensor x, Tensor w, Tensor scale, Tensor bias, int groups, int stride, int act) -> Tensor")
     lib_def.define("nonlocal_dot(Tensor x, Tensor tpg, int ci, Tensor wout, Tensor bout) -> Tensor")
     lib_def.define("nonlocal_dot_mfma(Tensor x, Tensor tpg, int ci, Tensor wout, Tensor bout) -> Tensor")
+    lib_def.define("lvc_encode(Tensor x, Tensor codewords, Tensor scale) -> Tensor")
+    lib_def.define("lvc_gate(Tensor E, Tensor a, Tensor b, Tensor fc_w, Tensor fc_b) -> Tensor")
+    lib_def.define("channel_fuse(Tensor a, Tensor? t, Tensor v, int mode) -> Tensor")
     lib_def.define("yolox_decode(Tensor[] levels, int num_classes, int in_h, int in_w, int mode=0, int sigmoid=3) -> Tensor")
     lib_def.define("nms(Tensor pred, int num_classes, int box_mode, float conf_thres, float nms_thres, int max_det) -> "
                    "(Tensor, Tensor, Tensor)")
@@ -234,6 +244,49 @@ def register():
             (View * 1)(_nhwc_view(y, "nonlocal_dot_mfma.y"))
         wa, ba = (C.c_void_p * 1)(wout.data_ptr()), (C.c_void_p * 1)(bout.data_ptr())
         check(lib.glsdet_nonlocal_mfma(xa, ta, 1, ci, wa, ba, ws.data_ptr(), nbytes, ya, _stream(x)), "nonlocal_dot_mfma")
+        return y
+
+    # ------------------------------------------------------------------ EVC block (csrc/evc.hip)
+    def _f32c(what, t, shape):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+            raise RuntimeError("%s must be a contiguous fp32 %s tensor, got %s %s" % (what, list(shape), t.dtype, tuple(t.shape)))
+
+    def lvc_encode(x, codewords, scale):
+        lib = _lib.load()
+        _need_cuda(x, codewords, scale)
+        xv = _nhwc_view(x, "lvc_encode.x")
+        n, h, w, c = x.shape
+        _f32c("lvc_encode: codewords", codewords, (64, c))
+        _f32c("lvc_encode: scale", scale, (64,))
+        nbytes = lib.glsdet_lvc_encode_workspace_bytes(n, h, w, c)
+        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=x.device)
+        E = torch.empty(n, 64, c, dtype=torch.float32, device=x.device)
+        check(lib.glsdet_lvc_encode(C.byref(xv), codewords.data_ptr(), scale.data_ptr(), ws.data_ptr(), nbytes, E.data_ptr(),
+                                    _stream(x)), "lvc_encode")
+        return E
+
+    def lvc_gate(E, a, b, fc_w, fc_b):
+        lib = _lib.load()
+        _need_cuda(E, a, b, fc_w, fc_b)
+        if E.dim() != 3 or E.shape[1] != 64:
+            raise RuntimeError("lvc_gate: E must be fp32 [N, 64, C]")
+        n, _, c = E.shape
+        for what, t, shape in (("E", E, (n, 64, c)), ("a", a, (64,)), ("b", b, (64,)), ("fc_w", fc_w, (c, c)), ("fc_b", fc_b, (c,))):
+            _f32c("lvc_gate: " + what, t, shape)
+        gam = torch.empty(n, c, dtype=torch.float32, device=E.device)
+        check(lib.glsdet_lvc_gate(E.data_ptr(), n, c, a.data_ptr(), b.data_ptr(), fc_w.data_ptr(), fc_b.data_ptr(), gam.data_ptr(),
+                                  _stream(E)), "lvc_gate")
+        return gam
+
+    def channel_fuse(a, t, v, mode):
+        lib = _lib.load()
+        _need_cuda(a, t, v)
+        n, _, _, c = a.shape
+        _f32c("channel_fuse: v", v, (n, c) if mode == 0 else (c,))
+        y = torch.empty_like(a)
+        av, yv = _nhwc_view(a, "channel_fuse.a"), _nhwc_view(y, "channel_fuse.y")
+        tv = C.byref(_nhwc_view(t, "channel_fuse.t")) if t is not None else None
+        check(lib.glsdet_channel_fuse(C.byref(av), tv, C.byref(yv), v.data_ptr(), mode, _stream(a)), "channel_fuse")
         return y
 
     # ------------------------------------------------------------------ yolox_decode
@@ -391,6 +444,9 @@ def register():
 
     for name, fn, fm in (("conv_bn_act", conv_bn_act, conv_bn_act_meta), ("conv2d_grouped", conv2d_grouped, conv2d_grouped_meta), ("nonlocal_dot", nonlocal_dot, lambda x, *a: torch.empty_like(x)),
                          ("nonlocal_dot_mfma", nonlocal_dot_mfma, lambda x, *a: torch.empty_like(x)),
+                         ("lvc_encode", lvc_encode, lambda x, c, s: x.new_empty((x.shape[0], 64, x.shape[3]), dtype=torch.float32)),
+                         ("lvc_gate", lvc_gate, lambda E, *a: E.new_empty((E.shape[0], E.shape[2]))),
+                         ("channel_fuse", channel_fuse, lambda a, *r: torch.empty_like(a)),
                          ("yolox_decode", yolox_decode, yolox_decode_meta), ("nms", nms, nms_meta),
                          ("soft_nms", soft_nms, soft_nms_meta), ("ufp_pack", ufp_pack, ufp_pack_meta), ("voc_ap", voc_ap, voc_ap_meta),
                          ("batched_nms", batched_nms, lambda b, s, i, t: b.new_empty((0,), dtype=torch.int64))):

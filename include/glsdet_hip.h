@@ -325,6 +325,39 @@ int glsdet_nonlocal_mfma(const glsdet_view* x, const glsdet_view* tpg, int32_t n
                          const glsdet_view* out, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * EVCBlock of the "centralized feature pyramid" (models/cfp/evc_blocks.py:214-308; additive exports of ABI 17).
+ *
+ * glsdet_lvc_encode: the codebook Encoding layer (models/cfp/Functions.py:25-84, 64 codewords) of every image of x:
+ *     A[n][k] = softmax_k( s_k |x_n - c_k|^2 ),   E[b][k][:] = sum_n A[n][k] (x_n - c_k)          n over the h * w pixels
+ *   x: NHWC view [n, h, w, C], f16 or f32, converted exactly; codewords fp32 [64][C]; scale fp32 [64]; E fp32 [n][64][C].
+ *   Evaluated in the expanded form, everything in fp32, the two products on v_mfma_f32_32x32x2_f32:
+ *     D = s_k * (fmaf(-2, x_n . c_k, |x_n|^2) + |c_k|^2),  A = expf(D - max_k D) / sum_k,  E = A^T X - (sum_n A) c.
+ *   A never reaches memory.  The pixels of an image are cut into slices of chunk = 128 * max(1, ceil(h w / 8192)) pixels
+ *   (a function of h * w only, at most 64 slices); every slice writes its partial A^T X and sum_n A to the workspace and a
+ *   second kernel adds the slices in ascending order: no atomics, the same bits on every run.
+ *   Refused (negative code, nothing launched) unless: C a multiple of 32 in [32, 640]; base and strides of x (a window's
+ *   offset is part of its base), codewords, scale and E multiples of 16 bytes; ws 256-byte aligned with ws_bytes >=
+ *   glsdet_lvc_encode_workspace_bytes(n, h, w, C) (0 for arguments out of range); h * w <= 2^24 and n <= 65535 (the grid
+ *   is (slices <= 64, n, ceil(C / 64))).
+ *
+ * glsdet_lvc_gate: LVCBlock.forward from the encoding to the gate (evc_blocks.py:223-238): BatchNorm1d(64) over [n, 64, C]
+ *   (per CODE; folded on the host to a_k, b_k), ReLU, the mean over the codes, fc, sigmoid.  fp32, in this order:
+ *     m = 0; for k = 0..63: m += fmaxf(fmaf(a_k, E[b][k][c], b_k), 0);   en[c] = m * (1 / 64)
+ *     v = fc_b[co]; for c = 0..C-1: v = fmaf(fc_w[co][c], en[c], v);     gam[b][co] = 1 / (1 + expf(-v))    (SIGMOID above)
+ *   E fp32 [n][64][C], fc_w fp32 [C][C] row-major, gam fp32 [n][C].  C as for glsdet_lvc_encode; E, fc_w, gam 16-byte aligned.
+ *
+ * glsdet_channel_fuse: NHWC views of one dtype and extent, 16 bytes per lane, fp32 arithmetic, one rounding; y may alias a.
+ *   mode 0: y = relu(fmaf(a, v[img][c], a))     v fp32 [n][C]   (`relu_(x + x * y)`, evc_blocks.py:239; t is not read)
+ *   mode 1: y = fmaf(v[c], t, a)                v fp32 [C]      (`x + layer_scale_1 * dw(norm1(x))`, evc_blocks.py:272)      */
+int64_t glsdet_lvc_encode_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t C);
+int glsdet_lvc_encode(const glsdet_view* x, const float* codewords, const float* scale, void* ws, int64_t ws_bytes,
+                      float* E, void* stream);
+int glsdet_lvc_gate(const float* E, int32_t n, int32_t C, const float* a_k, const float* b_k, const float* fc_w,
+                    const float* fc_b, float* gam, void* stream);
+int glsdet_channel_fuse(const glsdet_view* a, const glsdet_view* t, const glsdet_view* y, const float* v, int32_t mode,
+                        void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Patch_Conv_NonLocal_adapt_new: the data-dependent quadrant split (drone/models/new/Non_local_family.py:272-357)
  * The reference thresholds its SpatialAttention map (values under min + 0.75 (max - min) -> 0) and walks columns / rows in
  * Python until the running sum passes half of the total (`get_centroid`, :298-321: one device sync per step).  Here:
