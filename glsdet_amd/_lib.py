@@ -50,7 +50,22 @@ class CspDesc(C.Structure):
                [("act", C.c_int32), ("shortcut", C.c_int32)]
 
 
+class JpegDesc(C.Structure):
+    """glsdet_jpeg_desc: plain data, filled by glsdet_jpeg_parse"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32),
+                ("hs", C.c_int32 * 3), ("vs", C.c_int32 * 3),
+                ("mcus_x", C.c_int32), ("mcus_y", C.c_int32), ("restart_interval", C.c_int32),
+                ("blocks_x", C.c_int32 * 3), ("blocks_y", C.c_int32 * 3),
+                ("n_blocks", C.c_int64), ("scan_offset", C.c_int64),
+                ("tq", C.c_int32 * 3), ("td", C.c_int32 * 3), ("ta", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
 _SIGS = {
+    "glsdet_jpeg_parse": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(JpegDesc)]),
+    "glsdet_jpeg_entropy_decode": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(JpegDesc), C.c_void_p, C.c_void_p]),
+    "glsdet_jpeg_workspace_bytes": (C.c_int64, [C.POINTER(JpegDesc)]),
+    "glsdet_jpeg_reconstruct": (C.c_int, [C.POINTER(JpegDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_int64, C.c_int32, C.c_void_p]),
     "glsdet_csp_fused": (C.c_int, [C.POINTER(CspDesc), C.c_int32, C.c_void_p]),
     "glsdet_csp_fused_tune": (C.c_int, [C.POINTER(CspDesc), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "glsdet_conv2d_chain": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvChain), C.c_void_p]),

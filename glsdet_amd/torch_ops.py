@@ -44,6 +44,11 @@ allocated by the op on the input's device, nothing synchronises.  There is no CP
         :99-140, the nine picked miss rates of :26-62); the arrays of glsdet_voc_ap in include/glsdet_hip.h, built by
         glsdet_amd/eval/voc.py.  validate=True reads the offsets back (one synchronisation) and refuses non-monotone
         offsets or a pair_det that is no permutation; the kernels clamp either way.
+    glsdet::jpeg_reconstruct(coef, qtab, geometry, order) -> rgb uint8 [H, W, 3]
+        the device half of the baseline JPEG decoder (glsdet_jpeg_reconstruct: dequantise, libjpeg's ISLOW inverse DCT,
+        fancy upsampling, YCbCr -> RGB; what Image.open(path).convert("RGB") gives): coef int16 [n_blocks, 64] and qtab
+        uint16 (or int16 bits) [3, 64] as glsdet_jpeg_entropy_decode leaves them, geometry = width, height, ncomp, hs[3],
+        vs[3] (glsdet_amd.jpeg.geometry), order 0 RGB / 1 BGR
     glsdet::batched_nms(boxes, scores, idxs, iou_threshold) -> keep int64 [K]
         torchvision.ops.boxes.batched_nms's signature (utils_bbox.py:414-419), one image
 
@@ -157,6 +162,7 @@ def register():
     lib_def.define("voc_ap(Tensor dt_box, Tensor score, Tensor cls_off, Tensor pair_off, Tensor pair_det, Tensor gt_off, "
                    "Tensor gt_box, Tensor gt_difficult, Tensor n_gt, Tensor n_img, Tensor min_overlap, Tensor fppi_ref, "
                    "bool validate=False) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+    lib_def.define("jpeg_reconstruct(Tensor coef, Tensor qtab, int[] geometry, int order) -> Tensor")
     lib_def.define("batched_nms(Tensor boxes, Tensor scores, Tensor idxs, float iou_threshold) -> Tensor")
     impl = torch.library.Library("glsdet", "IMPL", "CUDA")
     cpu = torch.library.Library("glsdet", "IMPL", "CPU")
@@ -420,6 +426,24 @@ def register():
         i32, f64 = (lambda *s: score.new_empty(s, dtype=torch.int32)), (lambda *s: score.new_empty(s, dtype=torch.float64))
         return i32(T, nd), i32(T, nd), f64(T, nd), f64(T, nd), f64(T, nd), f64(T, C_, 16)
 
+    # ------------------------------------------------------------------ jpeg_reconstruct (csrc/jpeg.hip)
+    def jpeg_reconstruct(coef, qtab, geometry, order):
+        from .jpeg import desc_from_geometry
+        lib = _lib.load()
+        _need_cuda(coef, qtab)
+        d = desc_from_geometry(geometry)
+        if coef.dtype != torch.int16 or not coef.is_contiguous() or coef.numel() != d.n_blocks * 64 or d.n_blocks < 1:
+            raise RuntimeError("jpeg_reconstruct: coef must be a contiguous int16 [n_blocks, 64] tensor of the geometry's %d blocks"
+                               % d.n_blocks)
+        if qtab.dtype not in (torch.uint16, torch.int16) or not qtab.is_contiguous() or qtab.numel() != 192:
+            raise RuntimeError("jpeg_reconstruct: qtab must be a contiguous uint16 [3, 64] tensor")
+        out = torch.empty(d.height, d.width, 3, dtype=torch.uint8, device=coef.device)
+        nws = lib.glsdet_jpeg_workspace_bytes(C.byref(d))
+        ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=coef.device)
+        check(lib.glsdet_jpeg_reconstruct(C.byref(d), coef.data_ptr(), qtab.data_ptr(), ws.data_ptr(), nws, out.data_ptr(),
+                                          3 * d.width, order, _stream(coef)), "jpeg_reconstruct")
+        return out
+
     # ------------------------------------------------------------------ batched_nms (torchvision's signature)
     def batched_nms(boxes, scores, idxs, iou_threshold):
         _need_cuda(boxes, scores, idxs)
@@ -449,6 +473,8 @@ def register():
                          ("channel_fuse", channel_fuse, lambda a, *r: torch.empty_like(a)),
                          ("yolox_decode", yolox_decode, yolox_decode_meta), ("nms", nms, nms_meta),
                          ("soft_nms", soft_nms, soft_nms_meta), ("ufp_pack", ufp_pack, ufp_pack_meta), ("voc_ap", voc_ap, voc_ap_meta),
+                         ("jpeg_reconstruct", jpeg_reconstruct,
+                          lambda coef, qtab, geometry, order: coef.new_empty((geometry[1], geometry[0], 3), dtype=torch.uint8)),
                          ("batched_nms", batched_nms, lambda b, s, i, t: b.new_empty((0,), dtype=torch.int64))):
         impl.impl(name, fn)
         cpu.impl(name, no_cpu)

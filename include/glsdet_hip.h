@@ -787,6 +787,57 @@ int glsdet_voc_ap(const double* dt_box, const double* score, const int32_t* cls_
                   double* cls_out, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Baseline JPEG decoding (additive exports of ABI 17): the reference's `Image.open(path)` / `cv2.imread(path)`
+ * (drone/yolo.py, get_map*.py, ufpmp_det_eval.py:93), bit for bit what Pillow (libjpeg-turbo, JDCT_ISLOW, fancy
+ * upsampling) gives for the same bytes.  The serial part -- markers and Huffman -- runs on the host
+ * (csrc/jpeg_host.h, no HIP call: both host functions work without a GPU); everything at pixel rate runs on the device.
+ * Accepted streams: SOF0 (baseline, 8 bit, Huffman) with ONE interleaved scan; DQT with 8-bit entries, DHT, DRI, RSTn,
+ *   APPn, COM; grayscale (one 1x1 component) or three YCbCr components with luma 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0)
+ *   and 1x1 chroma.
+ * Refused, with a negative code and a message that names the reason: SOF1 / SOF2 / every other SOFn, arithmetic coding,
+ *   12-bit samples, 2 or 4 components, an Adobe APP14 marker whose transform is not 1 (or component ids 'R','G','B')
+ *   on a stream without a JFIF marker, other sampling factors, a scan that does not hold every component in frame order
+ *   or a marker other than EOI after it (several scans), 16-bit DQT entries, DNL or height 0, a table selector without
+ *   a table, a Huffman code that is in no table, a zero run past coefficient 63, a quantised coefficient outside
+ *   [-2048, 2047], a missing or out-of-order RSTn, data that ends before the last MCU or before EOI, and
+ *   width * height > 2^28.  Every read of `data` is checked against nbytes first.
+ * glsdet_jpeg_desc is plain data.  glsdet_jpeg_parse fills all of it; the entropy decoder parses the stream again and
+ *   refuses a descriptor that differs from its own; glsdet_jpeg_reconstruct recomputes mcus_*, blocks_* and n_blocks
+ *   from width, height, ncomp, hs, vs and refuses a descriptor that differs (they size every device index).
+ * glsdet_jpeg_entropy_decode (host buffers): coef = n_blocks * 64 int16, component by component, block raster inside a
+ *   component (blocks_x[c] per row), natural (row-major, de-zigzagged) order, NOT dequantised; qtab = [3][64] uint16,
+ *   row c = the table of component c in natural order, rows of absent components zero.
+ * glsdet_jpeg_reconstruct (device buffers coef, qtab, ws, dst): two kernels,
+ *   1. dequantise d = coef * q, libjpeg's jidctint.c (CONST_BITS 13, PASS1_BITS 2: pass 1 down the columns with
+ *      descale 11, pass 2 along the rows with descale 18, all in 64-bit integers like libjpeg's `long`), + 128,
+ *      saturated to 0..255 -> uint8 component planes of blocks_x*8 by blocks_y*8 in ws, one after the other;
+ *   2. jdsample.c's fancy upsampling of the chroma planes' REAL samples (dw = ceil(W*h_c/h_max) by dh alike; triangle
+ *      filters h2v1 / h2v2 with the edge samples replicated; plain replication where dw <= 2), jdcolor.c's 16-bit
+ *      fixed-point YCbCr -> RGB, each channel clamped, interleaved into rows 0..height-1 of dst, 3*width bytes each at
+ *      stride dst_row_bytes >= 3*width (the bytes of a row past 3*width are not written).  order 0 = RGB, 1 = BGR;
+ *      grayscale writes Y to all three.
+ *   ws: glsdet_jpeg_workspace_bytes(d) bytes (0 for a descriptor reconstruct would refuse), 16-byte aligned, contents
+ *   irrelevant.  Refused on the host, nothing launched: null pointers, a short or misaligned workspace,
+ *   dst_row_bytes < 3*width, order outside 0..1, an inconsistent descriptor.                                         */
+typedef struct glsdet_jpeg_desc {
+  int32_t width, height, ncomp;      /* ncomp 1 or 3 */
+  int32_t hs[3], vs[3];              /* sampling factors (0 for absent components) */
+  int32_t mcus_x, mcus_y, restart_interval;
+  int32_t blocks_x[3], blocks_y[3];  /* per component, padded to whole MCUs */
+  int64_t n_blocks;                  /* sum over components */
+  int64_t scan_offset;               /* first byte of the entropy-coded data */
+  int32_t tq[3], td[3], ta[3];       /* quantisation / DC / AC table selectors per component */
+  int32_t reserved;                  /* 0 */
+} glsdet_jpeg_desc;
+int glsdet_jpeg_parse(const unsigned char* data, int64_t nbytes, glsdet_jpeg_desc* d);
+int glsdet_jpeg_entropy_decode(const unsigned char* data, int64_t nbytes, const glsdet_jpeg_desc* d, int16_t* coef,
+                               uint16_t* qtab);
+int64_t glsdet_jpeg_workspace_bytes(const glsdet_jpeg_desc* d);
+int glsdet_jpeg_reconstruct(const glsdet_jpeg_desc* d, const int16_t* coef, const uint16_t* qtab, void* ws,
+                            int64_t ws_bytes, unsigned char* dst, int64_t dst_row_bytes, int32_t order /* 0 RGB, 1 BGR */,
+                            void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Plan: a recorded sequence of the calls above, replayed without Python in the loop and
  * capturable into one hipGraph (HIP streams + graphs instead of a tracing compiler).
  * Recording: glsdet_plan_begin(plan) makes every following entry-point call on this
