@@ -201,6 +201,10 @@ _SIGS = {
                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_int64, C.c_void_p]),
+    "glsdet_layernorm": (C.c_int, [C.POINTER(View), C.POINTER(View), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
+    "glsdet_window_attention": (C.c_int, [C.POINTER(View), C.POINTER(View), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_float, C.c_void_p]),
+    "glsdet_patch_merge": (C.c_int, [C.POINTER(View), C.POINTER(View), C.c_void_p]),
     "glsdet_plan_create": (C.c_void_p, []),
     "glsdet_plan_destroy": (None, [C.c_void_p]),
     "glsdet_plan_begin": (C.c_int, [C.c_void_p]),

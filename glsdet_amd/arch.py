@@ -258,6 +258,72 @@ def resnet_table(t: "_Table", p: str, depth: int = 50, base: int = 64, groups: i
             inplanes = planes * 4
 
 
+def swin_table(t: "_Table", p: str, embed_dims: int = 96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), window_size: int = 7,
+               mlp_ratio: int = 4, out_indices=(0, 1, 2, 3), patch_norm: bool = True, qkv_bias: bool = True, in_channels: int = 3):
+    """SwinTransformer (ufp/mmdet/models/backbones/swin.py:578-640), registration order: patch_embed, the stages (per block
+    norm1, attn.w_msa {table, index, qkv, proj}, norm2, ffn; then the stage's downsample {norm, reduction}), norm{i}.
+    The ffn.layers.0.0 / ffn.layers.1 names are those of mmcv 1.x's FFN module tree."""
+    def ln(q, c):
+        t[q + ".weight"] = (c,)
+        t[q + ".bias"] = (c,)
+
+    def lin(q, cin, cout, bias=True):
+        t[q + ".weight"] = (cout, cin)
+        if bias:
+            t[q + ".bias"] = (cout,)
+
+    t.plain(p + ".patch_embed.projection", in_channels, embed_dims, 4)
+    if patch_norm:
+        ln(p + ".patch_embed.norm", embed_dims)
+    c = embed_dims
+    n2 = window_size * window_size
+    for i, depth in enumerate(depths):
+        for j in range(depth):
+            q = "%s.stages.%d.blocks.%d" % (p, i, j)
+            ln(q + ".norm1", c)
+            t[q + ".attn.w_msa.relative_position_bias_table"] = ((2 * window_size - 1) ** 2, num_heads[i])
+            t[q + ".attn.w_msa.relative_position_index"] = (n2, n2)
+            lin(q + ".attn.w_msa.qkv", c, 3 * c, qkv_bias)
+            lin(q + ".attn.w_msa.proj", c, c)
+            ln(q + ".norm2", c)
+            lin(q + ".ffn.layers.0.0", c, mlp_ratio * c)
+            lin(q + ".ffn.layers.1", mlp_ratio * c, c)
+        if i < len(depths) - 1:
+            q = "%s.stages.%d.downsample" % (p, i)
+            if patch_norm:
+                ln(q + ".norm", 4 * c)
+            lin(q + ".reduction", 4 * c, 2 * c, bias=False)
+            c *= 2
+    for i in out_indices:
+        ln("%s.norm%d" % (p, i), embed_dims * 2 ** i)
+
+
+def swin_state_dict_shapes(embed_dims: int = 96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), window_size: int = 7,
+                           mlp_ratio: int = 4, out_indices=(0, 1, 2, 3), patch_norm: bool = True, qkv_bias: bool = True,
+                           in_channels: int = 3, prefix: str = "") -> "OrderedDict[str, Tuple[int, ...]]":
+    """the state dict of a bare SwinTransformer (prefix ''), or of one under a detector (prefix 'backbone')"""
+    t = _Table()
+    swin_table(t, prefix, embed_dims, depths, num_heads, window_size, mlp_ratio, out_indices, patch_norm, qkv_bias, in_channels)
+    return OrderedDict((k.lstrip("."), v) for k, v in t.items())
+
+
+def swindet_state_dict_shapes(kind: str, num_classes: int = 10, start_level: int = 0, num_outs: int = 5,
+                              add_extra_convs="on_output", stacked: int = 4, reg_max: int = 16,
+                              proxies_list=(2, 3, 2, 5, 4, 8, 8, 4, 3, 3), **swin) -> "OrderedDict[str, Tuple[int, ...]]":
+    """GFL ('gfl') / MPDet ('mpdet') on a Swin trunk: backbone (swin_table, options **swin), FPN over its out_indices, head"""
+    if kind not in ("gfl", "mpdet"):
+        raise ValueError("kind must be 'gfl' or 'mpdet'")
+    t = _Table()
+    swin_table(t, "backbone", **swin)
+    widths = [swin.get("embed_dims", 96) * 2 ** i for i in swin.get("out_indices", (0, 1, 2, 3))]
+    fpn_table(t, "neck", widths, 256, start_level, num_outs, add_extra_convs)
+    if kind == "gfl":
+        gfl_head_table(t, "bbox_head", num_classes, 256, 256, stacked, reg_max, num_outs)
+    else:
+        mp_head_table(t, "bbox_head", proxies_list, 256, 256, stacked, reg_max, num_outs)
+    return t
+
+
 def fpn_table(t: "_Table", p: str, in_channels, out_channels: int, start_level: int, num_outs: int, add_extra_convs):
     """fpn.py:105-148: all lateral convs, then all fpn convs (incl. the extra stride-2 ones)."""
     n_lat = len(in_channels) - start_level

@@ -52,6 +52,11 @@ class TableModule(nn.Module):
                 self.register_buffer(flat, torch.zeros(shape, dtype=torch.long))
             elif key.endswith("integral.project"):                        # gfl_head.py:32-33
                 self.register_buffer(flat, torch.linspace(0, shape[0] - 1, shape[0]))
+            elif key.endswith("relative_position_index"):                 # WindowMSA's buffer (swin.py:64-68)
+                from ..synth import synth_tensor
+                self.register_buffer(flat, torch.from_numpy(synth_tensor(key, tuple(shape), 0)))
+            elif key.endswith("relative_position_bias_table"):            # swin.py:59-61
+                self.register_parameter(flat, nn.Parameter(torch.zeros(shape), requires_grad=False))
             elif key.endswith("proxies"):
                 self.register_parameter(flat, nn.Parameter(torch.randn(shape) * 0.01, requires_grad=False))
             elif (key.endswith("weight") and len(shape) == 1) or len(shape) == 0:   # BN / GN gamma, mmcv Scale

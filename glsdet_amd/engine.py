@@ -929,6 +929,38 @@ class Engine:
                                            v.data_ptr(), mode, _stream_ptr(self.stream)), "channel_fuse")
         return out
 
+    # ---- Swin trunk (csrc/swin.hip)
+    def layernorm(self, x: TView, gamma: torch.Tensor, beta: torch.Tensor, eps: float, out: Optional[TView] = None,
+                  out_dtype: Optional[int] = None) -> TView:
+        """glsdet_layernorm over the channels of every token; gamma / beta fp32 [C] on the device; the output may have
+        another dtype than x (out_dtype, or out's)"""
+        if out is None:
+            out = self.tensor(x.n, x.h, x.w, x.c, x.dtype if out_dtype is None else out_dtype)
+        assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == x.c == beta.numel()
+        check(self.lib.glsdet_layernorm(C.byref(x.as_c()), C.byref(out.as_c()), gamma.data_ptr(), beta.data_ptr(), eps,
+                                        _stream_ptr(self.stream)), "layernorm")
+        return out
+
+    def window_attention(self, qkv: TView, table: torch.Tensor, qkv_bias: Optional[torch.Tensor], heads: int, ws: int,
+                         shift: int, scale: float, out: Optional[TView] = None) -> TView:
+        """glsdet_window_attention: qkv [n, H, W, 3C] -> [n, H, W, C]; table fp32 [(2 ws - 1)^2, heads] and qkv_bias fp32
+        [3C] (or None) on the device"""
+        if out is None:
+            out = self.tensor(qkv.n, qkv.h, qkv.w, qkv.c // 3, qkv.dtype)
+        assert table.dtype == torch.float32 and tuple(table.shape) == ((2 * ws - 1) ** 2, heads)
+        assert qkv_bias is None or (qkv_bias.dtype == torch.float32 and qkv_bias.numel() == qkv.c)
+        check(self.lib.glsdet_window_attention(C.byref(qkv.as_c()), C.byref(out.as_c()), table.data_ptr(),
+                                               qkv_bias.data_ptr() if qkv_bias is not None else None, heads, ws, shift,
+                                               scale, _stream_ptr(self.stream)), "window_attention")
+        return out
+
+    def patch_merge(self, x: TView, out: Optional[TView] = None) -> TView:
+        """glsdet_patch_merge: [n, H, W, C] -> [n, ceil(H / 2), ceil(W / 2), 4C] in nn.Unfold's channel order"""
+        if out is None:
+            out = self.tensor(x.n, (x.h + 1) // 2, (x.w + 1) // 2, 4 * x.c, x.dtype)
+        check(self.lib.glsdet_patch_merge(C.byref(x.as_c()), C.byref(out.as_c()), _stream_ptr(self.stream)), "patch_merge")
+        return out
+
     # ---- Patch_Conv_NonLocal_adapt_new: device-side quadrant split
     def attn_split(self, att: TView) -> torch.Tensor:
         """-> device int32[4] {row split, column split above it, column split from it on, 0} (glsdet_attn_split)."""

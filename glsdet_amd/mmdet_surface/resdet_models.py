@@ -16,7 +16,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..arch import _Table, fpn_table, gfl_head_table, gl_fusion_table, mp_head_table, resnet_table, resnext_width, RESNET_STAGE_BLOCKS
+from ..arch import (_Table, fpn_table, gfl_head_table, gl_fusion_table, mp_head_table, resnet_table, resnext_width, swin_table,
+                    RESNET_STAGE_BLOCKS)
 from ..drone.body import TableModule, _autotune
 from ..resdet import HipGflDetector
 from .registry import BACKBONES, DETECTORS, HEADS, NECKS, ConfigDict, build_backbone, build_head, build_neck
@@ -73,6 +74,61 @@ class ResNeXt(ResNet):
             raise TypeError("ResNeXt takes groups= and base_width=")
         super().__init__(_groups=int(groups), _base_width=int(base_width), **kwargs)
         self.groups, self.base_width = int(groups), int(base_width)
+
+
+@BACKBONES.register_module()
+class SwinTransformer(TableModule):
+    """ufp/mmdet/models/backbones/swin.py:466-762 with the reference's constructor signature.  Lowered: patch 4, strides
+    (4, 2, 2, 2), LayerNorm, GELU, head_dim 32, window_size 2..8, relative position bias only.  Refused with the argument named:
+    use_abs_pos_embed=True, with_cp, a non-GELU act_cfg, a non-LN norm_cfg, other strides / patch_size, window_size outside
+    2..8.  The drop_* rates are accepted: inference is the identity.  `pretrained`, `init_cfg`, `convert_weights` and
+    `frozen_stages` are accepted, stored and otherwise IGNORED, as on the ResNet surface: nothing is read here, weights arrive
+    through the detector's load_state_dict (init_detector's `checkpoint`, a local file).  A `pretrained` / init_cfg
+    checkpoint that is a URL is refused, so that a config which relies on a download fails early instead of running on
+    random weights."""
+
+    def __init__(self, pretrain_img_size=224, in_channels=3, embed_dims=96, patch_size=4, window_size=7, mlp_ratio=4,
+                 depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), strides=(4, 2, 2, 2), out_indices=(0, 1, 2, 3), qkv_bias=True,
+                 qk_scale=None, patch_norm=True, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.1, use_abs_pos_embed=False,
+                 act_cfg=dict(type="GELU"), norm_cfg=dict(type="LN"), with_cp=False, pretrained=None, convert_weights=False,
+                 frozen_stages=-1, init_cfg=None):
+        super().__init__()
+        assert not (init_cfg and pretrained), "init_cfg and pretrained cannot be specified at the same time"   # swin.py:559
+        if not (pretrained is None or isinstance(pretrained, str)):
+            raise TypeError("pretrained must be a str or None")
+        assert tuple(strides)[0] == patch_size, "Use non-overlapping patch embed."                            # swin.py:576
+        for name, val, ok in (("use_abs_pos_embed", bool(use_abs_pos_embed), False), ("with_cp", bool(with_cp), False),
+                              ("act_cfg", dict(act_cfg or {}).get("type"), "GELU"), ("norm_cfg", dict(norm_cfg or {}).get("type"), "LN"),
+                              ("strides", tuple(strides), (4, 2, 2, 2)), ("in_channels", in_channels, 3)):
+            if val != ok:
+                raise NotImplementedError("SwinTransformer(%s=%r) is not lowered (supported: %r)" % (name, val, ok))
+        if not 2 <= int(window_size) <= 8:
+            raise NotImplementedError("SwinTransformer(window_size=%r) is not lowered (supported: 2..8)" % (window_size,))
+        for ckpt in (pretrained, dict(init_cfg or {}).get("checkpoint")):
+            if ckpt is not None and "://" in str(ckpt):
+                raise NotImplementedError("SwinTransformer checkpoint %r: nothing is downloaded; load a local file through "
+                                          "init_detector(config, checkpoint)" % (ckpt,))
+        if len(depths) != len(num_heads) or any(embed_dims * 2 ** i != 32 * h for i, h in enumerate(num_heads)):
+            raise NotImplementedError("SwinTransformer(embed_dims=%r, num_heads=%r) is not lowered: every stage needs "
+                                      "head_dim 32" % (embed_dims, tuple(num_heads)))
+        assert max(out_indices) < len(depths)
+        self.embed_dims, self.depths, self.num_heads = int(embed_dims), tuple(depths), tuple(num_heads)
+        self.window_size, self.mlp_ratio, self.out_indices = int(window_size), int(mlp_ratio), tuple(out_indices)
+        self.qkv_bias, self.qk_scale, self.patch_norm = bool(qkv_bias), qk_scale, bool(patch_norm)
+        self.convert_weights, self.frozen_stages = convert_weights, frozen_stages
+        self.init_cfg = dict(type="Pretrained", checkpoint=pretrained) if isinstance(pretrained, str) else init_cfg   # swin.py:561-566
+        self.num_features = [int(embed_dims * 2 ** i) for i in range(len(depths))]
+        self.out_channels = self.num_features
+        t = _Table()
+        swin_table(t, "x", self.embed_dims, self.depths, self.num_heads, self.window_size, self.mlp_ratio, self.out_indices,
+                   self.patch_norm, self.qkv_bias, in_channels)
+        self._init_table(_Table((k[2:], v) for k, v in t.items()))
+
+    def detector_options(self) -> dict:
+        """the options of HipGflDetector(backbone='swin')"""
+        return dict(backbone="swin", embed_dims=self.embed_dims, depths=self.depths, num_heads=self.num_heads,
+                    window_size=self.window_size, mlp_ratio=self.mlp_ratio, out_indices=self.out_indices,
+                    patch_norm=self.patch_norm, qkv_bias=self.qkv_bias, qk_scale=self.qk_scale)
 
 
 @NECKS.register_module()
@@ -199,9 +255,9 @@ class SingleStageDetector(nn.Module):
         bbox_head.update(train_cfg=train_cfg)
         bbox_head.update(test_cfg=test_cfg)
         self.bbox_head = build_head(bbox_head)
-        if not isinstance(self.backbone, ResNet) or not isinstance(self.neck, FPN) or \
+        if not isinstance(self.backbone, (ResNet, SwinTransformer)) or not isinstance(self.neck, FPN) or \
                 not isinstance(self.bbox_head, (GFLHead, MPHead)):
-            raise NotImplementedError("%s is lowered for ResNet + FPN + GFLHead/MPHead" % type(self).__name__)
+            raise NotImplementedError("%s is lowered for ResNet / SwinTransformer + FPN + GFLHead/MPHead" % type(self).__name__)
         self.train_cfg, self.test_cfg = train_cfg, ConfigDict(test_cfg) if test_cfg is not None else None
         self.hip_dtype = hip_dtype
         self._det: Optional[HipGflDetector] = None
@@ -236,9 +292,12 @@ class SingleStageDetector(nn.Module):
             h, n = self.bbox_head, self.neck
             kind = "mpdet" if isinstance(h, MPHead) else "gfl"
             cfg = dict(start_level=n.start_level, num_outs=n.num_outs, add_extra_convs=n.add_extra_convs,
-                       stacked_convs=h.stacked_convs, strides=h.strides, reg_max=h.reg_max, depth=self.backbone.depth,
-                       out_indices=self.backbone.out_indices, groups=getattr(self.backbone, "groups", 1),
-                       base_width=getattr(self.backbone, "base_width", 4))
+                       stacked_convs=h.stacked_convs, strides=h.strides, reg_max=h.reg_max)
+            if isinstance(self.backbone, SwinTransformer):
+                cfg.update(self.backbone.detector_options())
+            else:
+                cfg.update(depth=self.backbone.depth, out_indices=self.backbone.out_indices,
+                           groups=getattr(self.backbone, "groups", 1), base_width=getattr(self.backbone, "base_width", 4))
             if kind == "mpdet":
                 cfg.update(proxies_list=tuple(h.proxies_list), gamma=float(h.gamma))
             cfg.update(gl_levels=list(n.gl_levels) if isinstance(n, GLFusionFPN) else [])

@@ -35,6 +35,7 @@ GL_AUG = int(os.environ.get("GLSDET_GL_AUG", "64"))
 
 RESNET_BN_EPS = 1e-5
 GN_EPS = 1e-5
+LN_EPS = 1e-5                                   # nn.LayerNorm's default: build_norm_layer(dict(type='LN'), c)
 STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3)}
 
 
@@ -179,6 +180,70 @@ class ResDetBuilder:
                                     cat=cat10 if (i == 0 and j == 0) else None)
             if i in out_indices:
                 outs.append(x)
+        return outs
+
+    # ------------------------------------------------------------------ Swin backbone
+    def _linear(self, p: str, x: TView, act: str = "none", res: Optional[TView] = None, out_dtype=None) -> TView:
+        """nn.Linear over the channels of every token = a 1x1 conv (the conv family's tuner and ConvDesc builder apply)"""
+        key = (p, "linear")
+        if key not in self._packed:
+            w = self.sd[p + ".weight"].float()
+            b = self.sd.get(p + ".bias")
+            self._packed[key] = self.e.pack_conv([(w.reshape(w.shape[0], w.shape[1], 1, 1), torch.ones(w.shape[0]),
+                                                   torch.zeros(w.shape[0]) if b is None else b.float())], x.c)
+        return self.e.conv(x, self._packed[key], 1, 0, act, res=res, out_dtype=out_dtype)
+
+    def _ln(self, p: str, x: TView, out_dtype=None) -> TView:
+        return self.e.layernorm(x, self._dev(p + ".weight", self.sd[p + ".weight"]), self._dev(p + ".bias", self.sd[p + ".bias"]),
+                                LN_EPS, out_dtype=out_dtype)
+
+    def swin_block(self, p: str, x: TView, heads: int, ws: int, shift: int, qk_scale: Optional[float] = None) -> TView:
+        """SwinBlock.forward (swin.py:357-377) on the fp32 residual stream x: both LayerNorms write the engine dtype (the
+        operand of the next linear); proj and the second FFN linear add the stream in their epilogue and store fp32."""
+        e = self.e
+        y = self._ln(p + ".norm1", x, e.dt)
+        a = p + ".attn.w_msa"
+        qkv = self._linear(a + ".qkv", y)
+        bq = self.sd.get(a + ".qkv.bias")
+        scale = float(np.float32(qk_scale or (x.c // heads) ** -0.5))
+        o = e.window_attention(qkv, self._dev(a + ".relative_position_bias_table", self.sd[a + ".relative_position_bias_table"]),
+                               None if bq is None else self._dev(a + ".qkv.bias", bq), heads, ws, shift, scale)
+        x = self._linear(a + ".proj", o, res=x, out_dtype=F32)
+        y = self._ln(p + ".norm2", x, e.dt)
+        h = self._linear(p + ".ffn.layers.0.0", y, "gelu")
+        return self._linear(p + ".ffn.layers.1", h, res=x, out_dtype=F32)
+
+    def swin(self, p: str, img: torch.Tensor, embed_dims: int = 96, depths: Sequence[int] = (2, 2, 6, 2),
+             num_heads: Sequence[int] = (3, 6, 12, 24), window_size: int = 7, mlp_ratio: int = 4,
+             out_indices: Sequence[int] = (0, 1, 2, 3), patch_norm: bool = True, qkv_bias: bool = True,
+             qk_scale: Optional[float] = None) -> List[TView]:
+        """SwinTransformer.forward (swin.py:744-762) -> the NHWC maps after norm{i}, in the engine dtype: what fpn() takes.
+        The residual stream between the blocks is fp32 in both modes.  The 4x4 stride-4 patch embedding is
+        a conv of the packed image, whose buffer is zero past H / W up to the next multiple of 4 (AdaptivePadding 'corner')."""
+        e = self.e
+        n, cin, H, W = img.shape
+        packed = e.tensor(n, -(-H // 4) * 4, -(-W // 4) * 4, -(-cin // 8) * 8)
+        e.nchw_pack(img, out=packed.window(0, H, 0, W))
+        x = e.conv(packed, self._pack(p + ".patch_embed.projection", [self._plain_part(p + ".patch_embed.projection")], packed.c),
+                   4, 0, "none", out_dtype=F32)
+        if x.c != embed_dims or (p + ".patch_embed.norm.weight" in self.sd) != patch_norm:
+            raise ValueError("%s.patch_embed does not match embed_dims=%d, patch_norm=%s" % (p, embed_dims, patch_norm))
+        if patch_norm:
+            x = self._ln(p + ".patch_embed.norm", x)
+        outs = []
+        for i, depth in enumerate(depths):
+            for j in range(depth):
+                x = self.swin_block("%s.stages.%d.blocks.%d" % (p, i, j), x, num_heads[i], window_size,
+                                    window_size // 2 if j % 2 else 0, qk_scale)
+            if i in out_indices:
+                outs.append(self._rec("%s.norm%d" % (p, i), self._ln("%s.norm%d" % (p, i), x, e.dt)))
+            if i < len(depths) - 1:
+                d = "%s.stages.%d.downsample" % (p, i)
+                u = e.patch_merge(x)
+                if patch_norm:                  # (without it the stream must already be the operand type: f32 mode only)
+                    u = self._ln(d + ".norm", u, e.dt)
+                assert u.dtype == e.dt, "patch_norm=False needs the f32 mode"
+                x = self._linear(d + ".reduction", u, out_dtype=F32)
         return outs
 
     # ------------------------------------------------------------------ GL-fusion plug-in (BASELINE config 3)
@@ -704,14 +769,20 @@ class _Compiled:
 class HipGflDetector(PlanBacked):
     """ResNet-50 + FPN + GFLHead ('gfl') or MPHead ('mpdet'); mmdet state-dict names.
     cfg keys: start_level, num_outs, add_extra_convs, stacked_convs, strides, reg_max,
-    proxies_list, gamma, depth, out_indices (defaults = the GFL r50-FPN / MPDet configs)."""
+    proxies_list, gamma, depth, out_indices (defaults = the GFL r50-FPN / MPDet configs).
+    backbone='swin' puts a SwinTransformer in the ResNet's place (embed_dims, depths, num_heads, window_size, mlp_ratio,
+    patch_norm, qkv_bias, qk_scale; out_indices is shared): ResDetBuilder.swin."""
 
     DEFAULTS = dict(start_level=1, num_outs=5, add_extra_convs="on_output", relu_before_extra_convs=False,
                     stacked_convs=4, strides=(8, 16, 32, 64, 128), reg_max=16, depth=50, out_indices=(0, 1, 2, 3),
                     proxies_list=(2, 3, 2, 5, 4, 8, 8, 4, 3, 3), gamma=10.0,
                     groups=1, base_width=4,  # ResNeXt backbone (groups > 1): checked against the state_dict's conv2 shapes
                     gl_levels=None,          # backbone outputs that get x + Patch_Conv_NonLocal_new(x) (None: those whose
-                    gl_assoc="auto")         # neck.gl_fusion.<i>.* keys exist in the state_dict); association of its products
+                    gl_assoc="auto",         # neck.gl_fusion.<i>.* keys exist in the state_dict); association of its products
+                    # backbone="swin": a SwinTransformer (swin.py:523-547) instead of the ResNet / ResNeXt; its options are
+                    # checked against the state_dict's shapes; out_indices is shared with the ResNet
+                    backbone="resnet", embed_dims=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), window_size=7,
+                    mlp_ratio=4, patch_norm=True, qkv_bias=True, qk_scale=None)
 
     def __init__(self, kind: str, state_dict, dtype: str = "f16", device: str = "cuda:0", autotune: bool = False, **cfg):
         if kind not in ("gfl", "mpdet"):
@@ -728,6 +799,10 @@ class HipGflDetector(PlanBacked):
                 g > 1 and w2.shape[0] != resnext_width(w1.shape[0], g, self.cfg["base_width"], w1.shape[0]))):
             raise ValueError("backbone.layer1.0.conv2.weight %s is not that of groups=%d, base_width=%d" %
                              (tuple(w2.shape), self.cfg["groups"], self.cfg["base_width"]))
+        if self.cfg["backbone"] not in ("resnet", "swin"):
+            raise ValueError("backbone must be 'resnet' or 'swin', got %r" % (self.cfg["backbone"],))
+        if self.cfg["backbone"] == "swin":
+            self._check_swin()
         if kind == "gfl":
             self.num_classes = self.sd["bbox_head.gfl_cls.weight"].shape[0]
         else:
@@ -735,10 +810,36 @@ class HipGflDetector(PlanBacked):
         super().__init__()                        # the plan cache: self._plans, its dict self._compiled and its lock
         self._aug: Dict[Tuple, dict] = {}         # detect_aug: private candidate buffers + merge buffers (under self._cache_lock)
 
+    _SWIN_OPTS = ("embed_dims", "depths", "num_heads", "window_size", "mlp_ratio", "out_indices", "patch_norm", "qkv_bias")
+
+    def _check_swin(self):
+        """the Swin options against the state_dict: its names and shapes must be exactly those the options describe"""
+        from .arch import swin_state_dict_shapes
+        c = self.cfg
+        if not 2 <= c["window_size"] <= 8:
+            raise ValueError("window_size must lie in 2..8, got %r" % (c["window_size"],))
+        if len(c["depths"]) != len(c["num_heads"]) or any(c["embed_dims"] * 2 ** i != 32 * h for i, h in enumerate(c["num_heads"])):
+            raise ValueError("embed_dims=%d with num_heads=%s: every stage needs head_dim 32" % (c["embed_dims"], tuple(c["num_heads"])))
+        if not c["patch_norm"] and self.dtype != "f32":
+            raise NotImplementedError("patch_norm=False in the f16 mode: the merge's fp32 output has no cast to the operand "
+                                      "type of reduction")
+        want = swin_state_dict_shapes(prefix="backbone", **{k: c[k] for k in self._SWIN_OPTS})
+        have = {k: tuple(v.shape) for k, v in self.sd.items() if k.startswith("backbone.")}
+        for k, s in want.items():
+            if have.get(k) != tuple(s):
+                raise ValueError("%s is %s in the state_dict, %s by the Swin options %s" % (
+                    k, have.get(k), tuple(s), {o: c[o] for o in self._SWIN_OPTS}))
+        extra = sorted(set(have) - set(want))
+        if extra:
+            raise ValueError("state_dict keys the Swin options do not describe: %s ..." % extra[:3])
+
     def _emit(self, eng: Engine, img: torch.Tensor, trace: Optional[dict] = None):
         b, c = ResDetBuilder(eng, self.sd), self.cfg
         b.trace = trace
-        stages = b.resnet("backbone", img, c["depth"], c["out_indices"])
+        if c["backbone"] == "swin":
+            stages = b.swin("backbone", img, qk_scale=c["qk_scale"], **{k: c[k] for k in self._SWIN_OPTS})
+        else:
+            stages = b.resnet("backbone", img, c["depth"], c["out_indices"])
         levels = c["gl_levels"]
         if levels is None:
             levels = [i for i in range(len(stages)) if "neck.gl_fusion.%d.feat_patchconv_lt_nonlocal.theta.weight" % i in self.sd]

@@ -32,6 +32,12 @@ def synth_tensor(key: str, shape: Tuple[int, ...], seed: int) -> np.ndarray:
         return np.zeros(shape, np.int64)
     if leaf == "_proxies_prob":
         return rng.uniform(0.1, 0.5, shape).astype(np.float32)
+    if leaf == "relative_position_bias_table":           # WindowMSA (swin.py:59-61): order 0.5, not the init's zeros
+        return (0.5 * rng.standard_normal(shape)).astype(np.float32)
+    if leaf == "relative_position_index":                # WindowMSA's buffer (swin.py:64-68), a function of the window alone
+        ws = int(round(math.sqrt(shape[0])))
+        ty, tx = np.divmod(np.arange(ws * ws), ws)
+        return ((ty[:, None] - ty[None, :] + ws - 1) * (2 * ws - 1) + (tx[:, None] - tx[None, :] + ws - 1)).astype(np.int64)
     if leaf == "running_var":
         return rng.uniform(0.5, 1.5, shape).astype(np.float32)
     if leaf == "running_mean":

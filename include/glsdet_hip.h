@@ -838,6 +838,53 @@ int glsdet_jpeg_reconstruct(const glsdet_jpeg_desc* d, const int16_t* coef, cons
                             void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Swin trunk (additive exports of ABI 17): the steps of ufp/mmdet/models/backbones/swin.py and of PatchMerging in
+ * ufp/mmdet/models/utils/transformer.py that are no convolution (csrc/swin.hip).  The linears around them (qkv, proj,
+ * the FFN, reduction) are 1x1 glsdet_conv2d calls.  All three record into a plan and replay from a captured graph;
+ * every refusal below happens on the host, before any launch.
+ *
+ * glsdet_layernorm: nn.LayerNorm over the channels of every token of an NHWC view (norm1 / norm2 of swin.py:361-367,
+ *   norm{i} of SwinTransformer.forward, the norms of PatchEmbed and of PatchMerging, transformer.py:383):
+ *     y[n,h,w,c] = (x[n,h,w,c] - mean) / sqrt(var + eps) * gamma[c] + beta[c],  var the biased variance over c.
+ *   fp32 statistics in TWO passes (mean first, then the sum of squared deviations -- never E[x^2] - mean^2), one wave
+ *   per token; the summation order is stated in csrc/swin.hip.  x and y have the same extent and may be strided views;
+ *   their dtypes may differ (an fp32 residual stream normalised into the fp16 operand of the next linear).
+ *   Refused: C no multiple of 32 or outside [32, 4096] (4096 covers the 4C of every merge up to Swin-L), extents that
+ *   differ, a negative or non-finite eps, gamma / beta (fp32 [C]) not 16-byte aligned, a y that overlaps x without being
+ *   the very same view (same base, strides and dtype: in place is allowed).
+ *
+ * glsdet_window_attention: ShiftWindowMSA.forward + WindowMSA.forward (swin.py:80-118, 179-253) WITHOUT the qkv and
+ *   proj linears.  qkv [n,H,W,3C] is the output of the qkv linear on the UNPADDED map, channel = which * C + head * 32 + d
+ *   (which = 0 q, 1 k, 2 v: the order of the reference's reshape to (3, heads, head_dim), swin.py:89-90); y [n,H,W,C]
+ *   receives softmax(q * scale . k^T + bias + mask) . v per window and head, channel = head * 32 + d, in UNSHIFTED
+ *   coordinates (swin.py:115, 237-248).  Padding to a multiple of ws (swin.py:186-188), the roll by -shift (:193-196),
+ *   window_partition / window_reverse and the roll back are index arithmetic in the kernel: nothing is copied.
+ *    (a) padding happens after norm1 and before qkv, so a padded token's q, k, v are qkv_bias (fp32 [3C], rounded to
+ *        the storage type as the linear would have stored it; NULL = no bias = zeros).  It takes full part in the
+ *        softmax of its window; its output row is dropped.
+ *    (b) the shift mask is -100 (not -inf) between tokens of different regions; the nine regions are those of
+ *        swin.py:199-219, taken on the PADDED map in SHIFTED coordinates, and are computed from coordinates.
+ *    (c) q is scaled before the product (swin.py:94).  bias_table is the module's relative_position_bias_table, fp32
+ *        [(2 ws - 1)^2][heads]; the kernel RESTATES relative_position_index (double_step_seq + transpose + flip,
+ *        swin.py:64-68): entry (i, j) = (ty_i - ty_j + ws - 1) * (2 ws - 1) + (tx_i - tx_j + ws - 1).  No index tensor
+ *        and no gathered [heads, N, N] table is passed.
+ *   S = q k^T and O = P v run on v_mfma_f32_32x32x2_f32 in both dtypes (fp32 images of q, k, v in LDS, P stays fp32);
+ *   N = ws^2 <= 64 tokens sit in a 64-wide tile whose columns past N are excluded from the softmax.  One workgroup per
+ *   (image, window, head), at most 4096 workgroups, each striding over the items.
+ *   Refused: head_dim other than 32 (heads * 32 != C), C no multiple of 32 or above 1024, ws outside 2..8, shift
+ *   outside 0..ws-1, qkv not [n,H,W,3C] of y's dtype, a non-finite scale, misaligned tables, a y whose span overlaps qkv's.
+ *
+ * glsdet_patch_merge: PatchMerging.forward up to, not including, norm and reduction (transformer.py:363-382): the
+ *   AdaptivePadding('corner') zero fill of an odd H / W (transformer.py:121-125) and nn.Unfold(kernel 2, stride 2), whose
+ *   channel order is channel-major:  y[n,oh,ow, 4 c + 2 kh + kw] = x[n, 2 oh + kh, 2 ow + kw, c] (0 past H / W).
+ *   The zeros take part in the LayerNorm that follows (a glsdet_layernorm call on y).
+ *   Refused: y not [n, ceil(H/2), ceil(W/2), 4C] of x's dtype, C no multiple of 8, a y whose span overlaps x's.      */
+int glsdet_layernorm(const glsdet_view* x, const glsdet_view* y, const float* gamma, const float* beta, float eps, void* stream);
+int glsdet_window_attention(const glsdet_view* qkv, const glsdet_view* y, const float* bias_table, const float* qkv_bias,
+                            int32_t heads, int32_t ws, int32_t shift, float scale, void* stream);
+int glsdet_patch_merge(const glsdet_view* x, const glsdet_view* y, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Plan: a recorded sequence of the calls above, replayed without Python in the loop and
  * capturable into one hipGraph (HIP streams + graphs instead of a tracing compiler).
  * Recording: glsdet_plan_begin(plan) makes every following entry-point call on this
