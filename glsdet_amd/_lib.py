@@ -253,6 +253,12 @@ def load():
     return lib
 
 
+def nonlocal_workspace_floats(n_sets, nimg, ci, cx):
+    """fp32 workspace of the non-local entry points (csrc/nonlocal_common.h: nl_layout): per set and image the eight
+    partial Gram slices [ci][ci] and the folded P [cx][ci]"""
+    return n_sets * nimg * (8 * ci * ci + cx * ci)
+
+
 def check(rc, what=""):
     if rc != 0:
         raise GlsdetError("%s failed (%d): %s" % (what or "glsdet call", rc,

@@ -1,7 +1,7 @@
 // Patch_Conv_NonLocal_adapt_new (drone/models/new/Non_local_family.py:272-357): the pieces around the non-local blocks
 // whose shapes depend on DATA.  The reference finds its quadrant split with Python loops that synchronise with the device
 // once per column / row (`if d.sum() > 0.5 * x.sum()`, :298-321); here one small kernel leaves the three split indices
-// in device memory and every consumer (non-local windows: misc.hip nl_window; row masks / selects below) reads them
+// in device memory and every consumer (non-local windows: nonlocal.hip nl_window; row masks / selects below) reads them
 // there: no host round trip, the whole block stays capturable in a hipGraph.
 #include "common.h"
 

@@ -15,6 +15,11 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
+// the 16-byte vector of a storage type: what one lane loads or stores of an NHWC pixel
+template <typename T> struct Vec16;
+template <> struct Vec16<f16> { typedef f16x8 type; static constexpr int N = 8; };
+template <> struct Vec16<float> { typedef f32x4 type; static constexpr int N = 4; };
+
 namespace glsdet {
 
 // ---- error plumbing -------------------------------------------------------------------

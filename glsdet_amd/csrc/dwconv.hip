@@ -6,10 +6,6 @@
 
 namespace glsdet {
 
-template <typename T> struct DwVec;
-template <> struct DwVec<f16> { typedef f16x8 type; static constexpr int N = 8; };
-template <> struct DwVec<float> { typedef f32x4 type; static constexpr int N = 4; };
-
 struct DwArgs {
   const unsigned char* x; const unsigned char* w; const float* scale; const float* bias; unsigned char* y;
   long x_sn, x_sh, x_sw, y_sn, y_sh, y_sw;
@@ -18,8 +14,8 @@ struct DwArgs {
 
 template <typename T>
 __global__ __launch_bounds__(256) void dwconv_kernel(const DwArgs a) {
-  typedef typename DwVec<T>::type V;
-  constexpr int VN = DwVec<T>::N;
+  typedef typename Vec16<T>::type V;
+  constexpr int VN = Vec16<T>::N;
   const int cchunks = a.C / VN;
   const long total = (long)a.N * a.Ho * a.Wo * cchunks;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {

@@ -17,8 +17,8 @@
 // The workgroups of the channel chunks of one slice each compute the logits of its pixels (the same instructions on the same
 // operands, hence the same A): at C = 256 that is 2.5 x the 0.28 GFLOP per image of the arithmetic, still far below a
 // microsecond of the fp32 matrix rate, and it keeps every accumulator in 16 registers for any C.
-// 256 threads = 2 x 2 waves on 32 x 32 accumulator tiles; lane maps as in nonlocal_mfma.hip.
-#include "common.h"
+// 256 threads = 2 x 2 waves on 32 x 32 accumulator tiles; lane maps in mfma_tile.h.
+#include "mfma_tile.h"
 
 namespace glsdet {
 
@@ -45,17 +45,11 @@ struct LvcArgs {
   int n, H, W, C, nsl, chunk;
 };
 
-template <typename T> struct LvcVec;
-template <> struct LvcVec<f16> { typedef f16x8 type; static constexpr int N = 8; };
-template <> struct LvcVec<float> { typedef f32x4 type; static constexpr int N = 4; };
-
-__device__ __forceinline__ int lvc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
-
 // grid (slice, image, 64-channel chunk)
 template <typename T>
 __global__ __launch_bounds__(256) void lvc_encode_kernel(const LvcArgs a) {
-  constexpr int VN = LvcVec<T>::N;
-  typedef typename LvcVec<T>::type V;
+  constexpr int VN = Vec16<T>::N;
+  typedef typename Vec16<T>::type V;
   constexpr int LD1 = 33, LDD = 65;
   __shared__ __attribute__((aligned(16))) float stage[2 * 64 * 33];          // phase 1: xs | cs as [64][33] each; phase 2: [pixel][64 channels]
   __shared__ float Ds[GLS_LVC_PT * LDD];
@@ -104,8 +98,7 @@ __global__ __launch_bounds__(256) void lvc_encode_kernel(const LvcArgs a) {
       {
         const float* pa = xs + (wm + l31) * LD1 + hi;
         const float* pb = cs + (wn + l31) * LD1 + hi;
-#pragma unroll
-        for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * s], pb[2 * s], acc, 0, 0, 0);
+        acc = mfma32_f32<16, 2, 2>(pa, pb, acc);
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -127,7 +120,7 @@ __global__ __launch_bounds__(256) void lvc_encode_kernel(const LvcArgs a) {
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int px = wm + lvc_row(r, lane), k = wn + l31;
+      const int px = wm + mfma32_row(r, lane), k = wn + l31;
       Ds[px * LDD + k] = scs[k] * (fmaf(-2.f, acc[r], xxs[px]) + ccs[k]);
     }
     // the 64 x 64 image of this chunk's channels for phase 2 (the staging area is free: everyone is past the last MFMA)
@@ -186,7 +179,7 @@ __global__ __launch_bounds__(256) void lvc_encode_kernel(const LvcArgs a) {
   if (wn < cw_) {
     float* o = a.Ep + (slot * GLS_LVC_K + wm) * C + c0 + wn + l31;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) o[(long)lvc_row(r, lane) * C] = accE[r];
+    for (int r = 0; r < 16; ++r) o[(long)mfma32_row(r, lane) * C] = accE[r];
   }
   if (blockIdx.z == 0 && tid < GLS_LVC_K) a.Sp[slot * GLS_LVC_K + tid] = ssum;
 }

@@ -1,47 +1,23 @@
 // The non-local block of glsdet_nonlocal_multi on the matrix cores, for wide blocks (ci a multiple of 32 up to 1280):
 // new/yolox10.py:236-266 runs Patch_Conv_NonLocal_new on dark3 / dark4 / dark5 with inter_channels = C
-// (Non_local_family.py:32-48): about 36 GFLOP per 8x800x1344 batch of YOLOX-s, on loops that misc.hip sized for ci = 64.
+// (Non_local_family.py:32-48): about 36 GFLOP per 8x800x1344 batch of YOLOX-s, on loops that nonlocal.hip sized for ci = 64.
 // DESIGN section 5 has the measured times of both kernel families; Engine picks per geometry from them.
 //
-// Same association, same workspace layout and the same determinism as misc.hip:
-//   nlm_gram   Gp[z][b][c1][c2] = sum_{j in slice z} phi[b,j,c1] g[b,j,c2]      (slices: the rule of glsdet_nonlocal_multi)
-//   nlm_fold   P[b][co][c1]     = (sum_c2 Wout[co][c2] (Gp[0] + Gp[1] + ... in this order)) * fl32(1 / N)
-//   nlm_apply  out[b,i,co]      = x[b,i,co] + bout[co] + sum_c1 theta[b,i,c1] P[b][co][c1]
+// Same association (nonlocal_common.h), same slice rule, same workspace layout and the same determinism as nonlocal.hip.
 // No atomics; a replay reproduces the bits.  No new rounding: theta / phi / g are read in the storage type, G, P, Wout and
-// bout are fp32.  The fp16 Gram runs on v_mfma_f32_32x32x16_f16 (a product of two fp16 numbers is exact in fp32), everything
-// else on v_mfma_f32_32x32x2_f32, which is a k-ordered fmaf chain: only the order of the sums differs from misc.hip.
+// bout are fp32.  The fp16 Gram runs on v_mfma_f32_32x32x16_f16, everything else on v_mfma_f32_32x32x2_f32 (mfma_tile.h
+// has the lane maps): only the order of the sums differs from nonlocal.hip.
 //
 // Every kernel: 256 threads = 2 x 2 waves, a wave owns one 32 x 32 accumulator tile of the workgroup's 64 x 64 tile; a wave
 // whose tile lies past a 32-multiple extent skips its MFMAs (wave-uniform) and its stores, never a barrier.
-// Lane maps: A[i = lane & 31][k = lane >> 5 (f32) | 8 (lane >> 5) + e (f16)], B[k][j = lane & 31],
-// C/D register r: row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31.
 #include <algorithm>
 
-#include "common.h"
+#include "mfma_tile.h"
+#include "nonlocal_common.h"
 
 namespace glsdet {
 
-#define GLS_NLM_SETS 4
 #define GLS_NLM_MAXC 1280
-struct NlmSet {
-  const unsigned char *x, *tpg;
-  unsigned char* out;
-  long xsn, xsh, xsw, tsn, tsh, tsw, osn, osh, osw;
-  const float *wout, *bout;
-  float *gram, *P;
-  int H, W, nsplit, jchunk;
-  float invN;
-};
-struct NlmArgs {
-  NlmSet s[GLS_NLM_SETS];
-  int n, nimg, ci, cx;
-};
-
-template <typename T> struct NlmVec;
-template <> struct NlmVec<f16> { typedef f16x8 type; static constexpr int N = 8; };
-template <> struct NlmVec<float> { typedef f32x4 type; static constexpr int N = 4; };
-
-__device__ __forceinline__ int nlm_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // ---------------------------------------------------------------- Gram
 // grid (tiles(c1) * tiles(c2), image, 8 * set + slice).  tpg is pixel-major, so K (the pixels) is outermost in memory:
@@ -52,11 +28,11 @@ __global__ __launch_bounds__(256) void nlm_gram_kernel(const NlmArgs a) {
   constexpr bool H16 = sizeof(T) == 2;
   constexpr int PX = H16 ? 64 : 32;                 // pixels per stage
   constexpr int LDH = PX + 8;                       // fp16 image: halves per channel row (144 B: 16-byte aligned rows)
-  constexpr int VN = NlmVec<T>::N, CPP = 64 / VN;   // 16-byte chunks per pixel and matrix
-  typedef typename NlmVec<T>::type V;
+  constexpr int VN = Vec16<T>::N, CPP = 64 / VN;    // 16-byte chunks per pixel and matrix
+  typedef typename Vec16<T>::type V;
   __shared__ __attribute__((aligned(16))) unsigned char smem[H16 ? 2 * 64 * LDH * 2 : 2 * PX * 64 * 4];
   const int q = blockIdx.z >> 3, z = blockIdx.z & 7;
-  const NlmSet& S = a.s[q];
+  const NlSet& S = a.s[q];
   if (z >= S.nsplit) return;                        // whole workgroup, before any barrier
   const int ci = a.ci, nb = (ci + 63) / 64;
   const int c1_0 = (blockIdx.x / nb) * 64, c2_0 = (blockIdx.x % nb) * 64;
@@ -67,9 +43,7 @@ __global__ __launch_bounds__(256) void nlm_gram_kernel(const NlmArgs a) {
   const int W = S.W, N = S.H * W;
   const int jbeg = z * S.jchunk, jend = min(N, jbeg + S.jchunk);
   const T* base = reinterpret_cast<const T*>(S.tpg) + b * S.tsn;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  f32x16 acc = mfma32_zero();
   for (int j0 = jbeg; j0 < jend; j0 += PX) {
     for (int t = threadIdx.x; t < 2 * PX * CPP; t += 256) {
       const int mat = t / (PX * CPP), r = t - mat * PX * CPP;
@@ -93,15 +67,11 @@ __global__ __launch_bounds__(256) void nlm_gram_kernel(const NlmArgs a) {
       if constexpr (H16) {
         const f16* ph = reinterpret_cast<const f16*>(smem) + (wm + l31) * LDH + 8 * hi;
         const f16* gg = reinterpret_cast<const f16*>(smem) + 64 * LDH + (wn + l31) * LDH + 8 * hi;
-#pragma unroll
-        for (int s = 0; s < PX / 16; ++s)
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(ph + 16 * s),
-                                                       *reinterpret_cast<const f16x8*>(gg + 16 * s), acc, 0, 0, 0);
+        acc = mfma32_f16<PX / 16>(ph, gg, acc);
       } else {
         const float* ph = reinterpret_cast<const float*>(smem) + hi * 64 + wm + l31;
         const float* gg = reinterpret_cast<const float*>(smem) + PX * 64 + hi * 64 + wn + l31;
-#pragma unroll
-        for (int s = 0; s < PX / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ph[s * 128], gg[s * 128], acc, 0, 0, 0);
+        acc = mfma32_f32<PX / 2, 128, 128>(ph, gg, acc);
       }
     }
     __syncthreads();
@@ -109,7 +79,7 @@ __global__ __launch_bounds__(256) void nlm_gram_kernel(const NlmArgs a) {
   if (active) {
     float* G = S.gram + (((long)z * a.nimg + b) * ci + c1_0 + wm) * ci + c2_0 + wn + l31;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) G[(long)nlm_row(r, lane) * ci] = acc[r];
+    for (int r = 0; r < 16; ++r) G[(long)mfma32_row(r, lane) * ci] = acc[r];
   }
 }
 
@@ -121,7 +91,7 @@ __global__ __launch_bounds__(256) void nlm_fold_kernel(const NlmArgs a) {
   constexpr int LD = GLS_NLM_KC + 1;
   __shared__ float wsm[64 * LD], gs[64 * LD];
   const int q = blockIdx.x / a.nimg, b = blockIdx.x - q * a.nimg;
-  const NlmSet& S = a.s[q];
+  const NlSet& S = a.s[q];
   const float* __restrict__ Gp = S.gram;
   const float* __restrict__ wout = S.wout;
   const int nsplit = S.nsplit, ci = a.ci, cx = a.cx;
@@ -130,9 +100,7 @@ __global__ __launch_bounds__(256) void nlm_fold_kernel(const NlmArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, hi = lane >> 5;
   const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
   const bool active = co0 + wm < cx && c1_0 + wn < ci;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  f32x16 acc = mfma32_zero();
   for (int c2_0 = 0; c2_0 < ci; c2_0 += GLS_NLM_KC) {
     const int kn = min(GLS_NLM_KC, ci - c2_0);        // 32 or 64
     const int cpr = kn / 4;
@@ -162,10 +130,7 @@ __global__ __launch_bounds__(256) void nlm_fold_kernel(const NlmArgs a) {
     if (active) {
       const float* pa = wsm + (wm + l31) * LD + hi;
       const float* pb = gs + (wn + l31) * LD + hi;
-      for (int s0 = 0; s0 < kn / 2; s0 += 8) {         // kn / 2 is 16 or 32
-#pragma unroll
-        for (int s = s0; s < s0 + 8; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * s], pb[2 * s], acc, 0, 0, 0);
-      }
+      for (int s0 = 0; s0 < kn / 2; s0 += 8) acc = mfma32_f32<8, 2, 2>(pa + 2 * s0, pb + 2 * s0, acc);      // kn / 2 is 16 or 32
     }
     __syncthreads();
   }
@@ -173,7 +138,7 @@ __global__ __launch_bounds__(256) void nlm_fold_kernel(const NlmArgs a) {
     float* P = S.P + ((long)b * cx + co0 + wm) * ci + c1_0 + wn + l31;
     const float invN = S.invN;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) P[(long)nlm_row(r, lane) * ci] = acc[r] * invN;
+    for (int r = 0; r < 16; ++r) P[(long)mfma32_row(r, lane) * ci] = acc[r] * invN;
   }
 }
 
@@ -184,13 +149,13 @@ __global__ __launch_bounds__(256) void nlm_fold_kernel(const NlmArgs a) {
 template <typename T>
 __global__ __launch_bounds__(256) void nlm_apply_kernel(const NlmArgs a) {
   constexpr int LD = GLS_NLM_KC + 1;
-  constexpr int VN = NlmVec<T>::N;
-  typedef typename NlmVec<T>::type V;
+  constexpr int VN = Vec16<T>::N;
+  typedef typename Vec16<T>::type V;
   __shared__ float sm[2 * 64 * LD];                  // theta tile | P tile; afterwards the 64 x (64 + 1) accumulator image
   float* th = sm;
   float* pr = sm + 64 * LD;
   const int q = blockIdx.y / a.nimg, b = blockIdx.y - q * a.nimg;
-  const NlmSet& S = a.s[q];
+  const NlSet& S = a.s[q];
   const int W = S.W, N = S.H * W, ci = a.ci, cx = a.cx;
   const int j0 = blockIdx.x * 64, co0 = blockIdx.z * 64;
   if (j0 >= N) return;                               // whole workgroup: this set is smaller than the largest one
@@ -199,21 +164,14 @@ __global__ __launch_bounds__(256) void nlm_apply_kernel(const NlmArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, hi = lane >> 5;
   const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
   const bool active = j0 + wm < N && co0 + wn < cx;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  f32x16 acc = mfma32_zero();
   for (int c0 = 0; c0 < ci; c0 += GLS_NLM_KC) {
     const int kn = min(GLS_NLM_KC, ci - c0);          // 32 or 64
     const int cpr = kn / VN;
     for (int idx = threadIdx.x; idx < 64 * cpr; idx += 256) {
       const int r = idx / cpr, ch = idx - r * cpr;
       const int jr = j0 + r;
-      V v;
-#pragma unroll
-      for (int k = 0; k < VN; ++k) v[k] = (T)0.f;
-      if (jr < N) v = *reinterpret_cast<const V*>(tbase + (long)(jr / W) * S.tsh + (long)(jr % W) * S.tsw + c0 + ch * VN);
-#pragma unroll
-      for (int k = 0; k < VN; ++k) th[r * LD + ch * VN + k] = (float)v[k];
+      stage_f32(th + r * LD + ch * VN, tbase + (long)(jr / W) * S.tsh + (long)(jr % W) * S.tsw + c0 + ch * VN, jr < N);
     }
     const int cp4 = kn / 4;
     for (int idx = threadIdx.x; idx < 64 * cp4; idx += 256) {
@@ -227,17 +185,14 @@ __global__ __launch_bounds__(256) void nlm_apply_kernel(const NlmArgs a) {
     if (active) {
       const float* pa = th + (wm + l31) * LD + hi;
       const float* pb = pr + (wn + l31) * LD + hi;
-      for (int s0 = 0; s0 < kn / 2; s0 += 8) {         // kn / 2 is 16 or 32
-#pragma unroll
-        for (int s = s0; s < s0 + 8; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * s], pb[2 * s], acc, 0, 0, 0);
-      }
+      for (int s0 = 0; s0 < kn / 2; s0 += 8) acc = mfma32_f32<8, 2, 2>(pa + 2 * s0, pb + 2 * s0, acc);      // kn / 2 is 16 or 32
     }
     __syncthreads();
   }
   float* so = sm;                                    // [64 pixels][64 + 1]: 4160 floats of the 8320
   if (active) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) so[(wm + nlm_row(r, lane)) * LD + wn + l31] = acc[r];
+    for (int r = 0; r < 16; ++r) so[(wm + mfma32_row(r, lane)) * LD + wn + l31] = acc[r];
   }
   __syncthreads();
   constexpr int CPP = 64 / VN;
@@ -261,23 +216,19 @@ __global__ __launch_bounds__(256) void nlm_apply_kernel(const NlmArgs a) {
 using namespace glsdet;
 
 extern "C" int64_t glsdet_nonlocal_mfma_workspace_bytes(int32_t n, int32_t n_sets, int32_t ci, int32_t cx) {
-  if (n < 1 || n_sets < 1 || n_sets > GLS_NLM_SETS || ci < 1 || cx < 1) return 0;
-  const int64_t floats = (int64_t)n_sets * n * (8LL * ci * ci + (int64_t)cx * ci);
-  return (floats * 4 + 255) / 256 * 256;
+  if (n < 1 || n_sets < 1 || n_sets > GLS_NL_SETS || ci < 1 || cx < 1) return 0;
+  return (n_sets * nl_layout(n, ci, cx).per_set * 4 + 255) / 256 * 256;
 }
 
 extern "C" int glsdet_nonlocal_mfma(const glsdet_view* x, const glsdet_view* tpg, int32_t n_sets, int32_t ci,
                                     const float* const* wout, const float* const* bout, void* ws, int64_t ws_bytes,
                                     const glsdet_view* out, void* stream) {
   if (!x || !tpg || !out || !wout || !bout || !ws) GLS_FAIL(GLSDET_E_ARG, "nonlocal_mfma: null argument");
-  if (n_sets < 1 || n_sets > GLS_NLM_SETS) GLS_FAIL(GLSDET_E_ARG, "nonlocal_mfma: 1..%d sets, got %d", GLS_NLM_SETS, n_sets);
+  if (n_sets < 1 || n_sets > GLS_NL_SETS) GLS_FAIL(GLSDET_E_ARG, "nonlocal_mfma: 1..%d sets, got %d", GLS_NL_SETS, n_sets);
   if (ci < 32 || ci % 32 || ci > GLS_NLM_MAXC)
     GLS_FAIL(GLSDET_E_ARG, "nonlocal_mfma: ci must be a multiple of 32 in [32, %d], got %d", GLS_NLM_MAXC, ci);
   NlmArgs a = {};
-  a.n = n_sets;
-  a.ci = ci;
-  a.cx = x[0].c;
-  a.nimg = x[0].n;
+  a.n = n_sets; a.ci = ci; a.cx = x[0].c; a.nimg = x[0].n;
   const int dt = x[0].dtype;
   if (dt != GLSDET_F16 && dt != GLSDET_F32) GLS_FAIL(GLSDET_E_ARG, "nonlocal_mfma: dtype must be f16 or f32, got %d", dt);
   if (a.cx < 32 || a.cx % 32 || a.cx > GLS_NLM_MAXC)
@@ -286,38 +237,15 @@ extern "C" int glsdet_nonlocal_mfma(const glsdet_view* x, const glsdet_view* tpg
   if ((uintptr_t)ws & 255) GLS_FAIL(GLSDET_E_ALIGN, "nonlocal_mfma: workspace must be 256-byte aligned");
   const int64_t need = glsdet_nonlocal_mfma_workspace_bytes(a.nimg, n_sets, ci, a.cx);
   if (ws_bytes < need) GLS_FAIL(GLSDET_E_ARG, "nonlocal_mfma: workspace of %ld bytes, %ld needed", (long)ws_bytes, (long)need);
-  const long per_set = (long)a.nimg * (8L * ci * ci + (long)a.cx * ci);      // floats of workspace per set
   OpRecord op;
   op.kind = 4;
   op.flops = op.bytes = 0;
   int maxN = 0;
   for (int q = 0; q < n_sets; ++q) {
     int rc;
-    if ((rc = check_view(x[q], "nonlocal_mfma.x"))) return rc;
-    if ((rc = check_view(tpg[q], "nonlocal_mfma.tpg"))) return rc;
-    if ((rc = check_view(out[q], "nonlocal_mfma.out"))) return rc;
-    if (x[q].dtype != dt || out[q].dtype != dt || tpg[q].dtype != dt)
-      GLS_FAIL(GLSDET_E_ARG, "nonlocal_mfma: set %d: x / tpg / out must share one dtype", q);
-    if (x[q].c != a.cx || x[q].n != a.nimg) GLS_FAIL(GLSDET_E_ARG, "nonlocal_mfma: the sets must agree in n and channels");
-    if (!same_extent(x[q], out[q])) GLS_FAIL(GLSDET_E_ARG, "nonlocal_mfma: set %d: x / out extent mismatch", q);
-    if (tpg[q].n != x[q].n || tpg[q].h != x[q].h || tpg[q].w != x[q].w || tpg[q].c < 3 * ci)
-      GLS_FAIL(GLSDET_E_ARG, "nonlocal_mfma: set %d: theta|phi|g view must be [n,h,w,>=3*ci]", q);
     if ((long)x[q].h * x[q].w > (1L << 24)) GLS_FAIL(GLSDET_E_ARG, "nonlocal_mfma: set %d: more than 2^24 pixels", q);
-    if (!wout[q] || !bout[q]) GLS_FAIL(GLSDET_E_ARG, "nonlocal_mfma: null weight");
-    if (((uintptr_t)wout[q] & 15) || ((uintptr_t)bout[q] & 15)) GLS_FAIL(GLSDET_E_ALIGN, "nonlocal_mfma: wout / bout must be 16-byte aligned");
-    NlmSet& S = a.s[q];
-    const int N = x[q].h * x[q].w;
-    S.x = (const unsigned char*)x[q].base; S.tpg = (const unsigned char*)tpg[q].base; S.out = (unsigned char*)out[q].base;
-    S.xsn = x[q].sn; S.xsh = x[q].sh; S.xsw = x[q].sw;
-    S.tsn = tpg[q].sn; S.tsh = tpg[q].sh; S.tsw = tpg[q].sw;
-    S.osn = out[q].sn; S.osh = out[q].sh; S.osw = out[q].sw;
-    S.wout = wout[q]; S.bout = bout[q];
-    S.gram = (float*)ws + q * per_set;
-    S.P = S.gram + (long)a.nimg * 8 * ci * ci;
-    S.H = x[q].h; S.W = x[q].w;
-    S.nsplit = N >= 1024 ? 8 : (N >= 256 ? 4 : 1);
-    S.jchunk = (((N + S.nsplit - 1) / S.nsplit) + 63) / 64 * 64;
-    S.invN = 1.0f / (float)N;
+    if ((rc = nl_build_set("nonlocal_mfma", a, q, dt, x[q], tpg[q], out[q], wout[q], bout[q], (float*)ws, true, true))) return rc;
+    const int N = a.s[q].H * a.s[q].W;
     maxN = std::max(maxN, N);
     // the count of the association these kernels run: Gram 2 N ci^2, fold 2 cx ci^2, apply 2 N ci cx per image
     op.flops += (double)a.nimg * (2.0 * N * ci * (double)ci + 2.0 * a.cx * ci * (double)ci + 2.0 * N * ci * (double)a.cx);
@@ -327,17 +255,9 @@ extern "C" int glsdet_nonlocal_mfma(const glsdet_view* x, const glsdet_view* tpg
   op.launch = [=](hipStream_t st) -> int {
     const int nbi = (a.ci + 63) / 64, nbx = (a.cx + 63) / 64;
     const dim3 g1(nbi * nbi, a.nimg, 8 * a.n), g2(a.nimg * a.n, nbx, nbi), g3((maxN + 63) / 64, a.nimg * a.n, nbx);
-    if (dt == GLSDET_F16) {
-      hipLaunchKernelGGL(nlm_gram_kernel<f16>, g1, dim3(256), 0, st, a);
-      hipLaunchKernelGGL(nlm_fold_kernel, g2, dim3(256), 0, st, a);
-      hipLaunchKernelGGL(nlm_apply_kernel<f16>, g3, dim3(256), 0, st, a);
-    } else {
-      hipLaunchKernelGGL(nlm_gram_kernel<float>, g1, dim3(256), 0, st, a);
-      hipLaunchKernelGGL(nlm_fold_kernel, g2, dim3(256), 0, st, a);
-      hipLaunchKernelGGL(nlm_apply_kernel<float>, g3, dim3(256), 0, st, a);
-    }
-    GLS_HIP(hipGetLastError());
-    return 0;
+    if (dt == GLSDET_F16) return nl_launch<nlm_gram_kernel<f16>, nlm_fold_kernel, nlm_apply_kernel<f16>>(st, a, g1, g2, g3, 0, 0);
+    return nl_launch<nlm_gram_kernel<float>, nlm_fold_kernel, nlm_apply_kernel<float>>(st, a, g1, g2, g3, 0, 0);
   };
   return submit(std::move(op), stream);
 }
+

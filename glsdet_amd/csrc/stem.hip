@@ -563,10 +563,6 @@ __global__ __launch_bounds__(256) void resnet_stem_kernel(const RStemArgs a) {
   (void)P_BYTES; (void)E_BYTES;
 }
 
-template <typename T> struct StemVec;
-template <> struct StemVec<f16> { typedef f16x8 type; };
-template <> struct StemVec<float> { typedef f32x4 type; };
-
 // The same stem with the 3x3 stride-2 max pool that follows it (resnet.py:637 `x = self.maxpool(x)`) in the epilogue: the
 // 275 MB conv output is neither written nor read by a pooling pass (378 + 344 MB -> 172 MB).  A workgroup owns a 4 x 8
 // tile of POOLED pixels = a 9 x 17 tile of conv pixels (1.2x recompute at the tile seams), computed as above into LDS
@@ -697,7 +693,7 @@ __global__ __launch_bounds__(256) void resnet_stem_pool_kernel(const RStemArgs a
         const int py = pq / QW, px = pq - py * QW;
         const int ho = qy0 + py, wo = qx0 + px;
         if (ho < a.Ho && wo < a.Wo) {
-          typedef typename StemVec<T>::type V;
+          typedef typename Vec16<T>::type V;
           V m = *reinterpret_cast<const V*>(sP + ((2 * py) * CW + 2 * px) * ORS + cq * 16);
 #pragma unroll
           for (int d = 1; d < 9; ++d) {

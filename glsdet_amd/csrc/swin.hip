@@ -29,7 +29,7 @@
 //   O[i][d] = sum_j P[i][j] v[j][d]                              the same MFMA, j ascending
 // Both storage types run the fp32 MFMA on fp32 images of q, k, v in LDS: P never leaves fp32.
 // LDS 43.4 KiB (q, k, v as [64][33], S / P as [64][65], the token table), no scratch, two 16-register accumulators.
-#include "common.h"
+#include "mfma_tile.h"
 
 #include <cmath>
 
@@ -161,14 +161,12 @@ struct WinArgs {
   long items;
 };
 
-__device__ __forceinline__ int win_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
-
 template <typename T>
 __global__ __launch_bounds__(128) void window_attention_kernel(const WinArgs a) {
-  constexpr int VN = 16 / (int)sizeof(T);
+  constexpr int VN = Vec16<T>::N;
   constexpr int CPR = 32 / VN;                  // 16-byte chunks of one head of one token
   constexpr int LDQ = 33, LDP = 65;
-  typedef T __attribute__((ext_vector_type(VN))) V;
+  typedef typename Vec16<T>::type V;
   __shared__ float qkv_s[3 * 64 * LDQ];         // q~ | k | v as [token][33]
   __shared__ float ss[64 * LDP];                // S, then P: [query][key]
   __shared__ int tpy[64], tpx[64], tty[64], ttx[64], treg[64];      // source pixel (-1: padded), window coordinates, region
@@ -246,16 +244,12 @@ __global__ __launch_bounds__(128) void window_attention_kernel(const WinArgs a) 
       const float* pa = qs + (wm + l31) * LDQ + hi;
       const float* pb0 = ks + l31 * LDQ + hi;
       const float* pb1 = ks + (32 + l31) * LDQ + hi;
-#pragma unroll
-      for (int s = 0; s < 16; ++s) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * s], pb0[2 * s], acc0, 0, 0, 0);
-      if (N > 32) {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * s], pb1[2 * s], acc1, 0, 0, 0);
-      }
+      acc0 = mfma32_f32<16, 2, 2>(pa, pb0, acc0);
+      if (N > 32) acc1 = mfma32_f32<16, 2, 2>(pa, pb1, acc1);
       const int span = 2 * ws - 1;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int i = wm + win_row(r, lane);
+        const int i = wm + mfma32_row(r, lane);
         if (i < N) {
           const int iy = tty[i] + ws - 1, ix = ttx[i] + ws - 1, ir = treg[i];
 #pragma unroll
@@ -302,11 +296,11 @@ __global__ __launch_bounds__(128) void window_attention_kernel(const WinArgs a) 
       const float* pa = ss + (wm + l31) * LDP + hi;
       const float* pb = vs + hi * LDQ + l31;
       const int steps = (N + 1) >> 1;
-      for (int s = 0; s < steps; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * s], pb[2 * s * LDQ], acc, 0, 0, 0);
+      for (int s = 0; s < steps; ++s) acc = mfma32_f32<1, 2, 2 * LDQ>(pa + 2 * s, pb + 2 * s * LDQ, acc);
       T* yb = reinterpret_cast<T*>(a.y) + img * a.ysn + head * 32 + l31;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int i = wm + win_row(r, lane);
+        const int i = wm + mfma32_row(r, lane);
         if (i < N && tpy[i] >= 0) yb[(long)tpy[i] * a.ysh + (long)tpx[i] * a.ysw] = (T)acc[r];
       }
     }

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import F16, F32, ACT, View, ConvChain, ConvDesc, check
+from ._lib import F16, F32, ACT, View, ConvChain, ConvDesc, check, nonlocal_workspace_floats
 
 _TORCH_DT = {F16: torch.float16, F32: torch.float32}
 _ESIZE = {F16: 2, F32: 4}
@@ -833,7 +833,7 @@ class Engine:
                   out: Optional[TView] = None) -> TView:
         if out is None:
             out = self.tensor(x.n, x.h, x.w, x.c, x.dtype)
-        ws = self.raw(x.n * (8 * ci * ci + x.c * ci) * 4)   # 8 partial Gram slices + folded P
+        ws = self.raw(nonlocal_workspace_floats(1, x.n, ci, x.c) * 4)
         check(self.lib.glsdet_nonlocal(C.byref(x.as_c()), C.byref(tpg.as_c()), ci, wout.data_ptr(), bout.data_ptr(),
                                        ws.data_ptr(), C.byref(out.as_c()), _stream_ptr(self.stream)), "nonlocal")
         return out
@@ -895,7 +895,7 @@ class Engine:
             ws = self.raw(nbytes)
             if self.lib.glsdet_nonlocal_mfma(xa, ta, n, ci, wa, ba, ws.data_ptr(), nbytes, oa, _stream_ptr(self.stream)) == 0:
                 return outs
-        ws = self.raw(n * xs[0].n * (8 * ci * ci + xs[0].c * ci) * 4)
+        ws = self.raw(nonlocal_workspace_floats(n, xs[0].n, ci, xs[0].c) * 4)
         check(self.lib.glsdet_nonlocal_multi(xa, ta, n, ci, wa, ba, ws.data_ptr(), oa, _stream_ptr(self.stream)),
               "nonlocal_multi")
         return outs
@@ -971,7 +971,7 @@ class Engine:
 
     def nonlocal_split(self, x: TView, tpgs: Sequence[TView], ci: int, wouts, bouts, out: TView, split: torch.Tensor,
                        shift: int = 0) -> TView:
-        ws = self.raw(4 * x.n * (8 * ci * ci + x.c * ci) * 4)
+        ws = self.raw(nonlocal_workspace_floats(4, x.n, ci, x.c) * 4)
         ta = (View * 4)(*[t.as_c() for t in tpgs])
         wa = (C.c_void_p * 4)(*[w.data_ptr() for w in wouts])
         ba = (C.c_void_p * 4)(*[b.data_ptr() for b in bouts])

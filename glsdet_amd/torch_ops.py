@@ -62,7 +62,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import F16, F32, ConvDesc, View, check
+from ._lib import F16, F32, ConvDesc, View, check, nonlocal_workspace_floats
 
 _DT = {torch.float16: F16, torch.float32: F32}
 
@@ -229,7 +229,7 @@ def register():
                 tuple(wout.shape) != (x.shape[3], ci) or bout.numel() != x.shape[3] or tpg.shape[3] < 3 * ci:
             raise RuntimeError("nonlocal_dot: wout fp32 [C, ci], bout fp32 [C], tpg NHWC with >= 3*ci channels")
         y = torch.empty_like(x)
-        ws = torch.empty(x.shape[0] * (8 * ci * ci + x.shape[3] * ci), dtype=torch.float32, device=x.device)
+        ws = torch.empty(nonlocal_workspace_floats(1, x.shape[0], ci, x.shape[3]), dtype=torch.float32, device=x.device)
         check(lib.glsdet_nonlocal(C.byref(_nhwc_view(x, "nonlocal_dot.x")), C.byref(_nhwc_view(tpg, "nonlocal_dot.tpg")), ci,
                                   wout.data_ptr(), bout.data_ptr(), ws.data_ptr(), C.byref(_nhwc_view(y, "nonlocal_dot.y")),
                                   _stream(x)), "nonlocal_dot")

@@ -1,5 +1,5 @@
 """An independent, deliberately naive reference of the data-dependent attention path (glsdet_amd/csrc/adapt.hip, the
-windowed non-local block of misc.hip, dwconv.hip) and the input builders of its differential tests.  TEST INFRASTRUCTURE
+windowed non-local block of nonlocal.hip, dwconv.hip) and the input builders of its differential tests.  TEST INFRASTRUCTURE
 ONLY; imports nothing from `oracle` -- it is the second opinion that tests/test_attention_reference.py holds against the
 oracle and tests/test_attention_fuzz.py against the kernels.
 

@@ -1,5 +1,5 @@
 """float64 reference, exact-arithmetic data regime and case lists of the non-local block kernels (nl_gram / nl_fold /
-nl_apply and nl_window of glsdet_amd/csrc/misc.hip, behind glsdet_nonlocal, glsdet_nonlocal_multi, glsdet_nonlocal_split).
+nl_apply and nl_window of glsdet_amd/csrc/nonlocal.hip, behind glsdet_nonlocal, glsdet_nonlocal_multi, glsdet_nonlocal_split).
 
 The reference (`nonlocal_block`) is the definition in its original order, on one window: f = theta phi^T / N (N x N),
 y = f g, out = x + y Wout^T + b.  The kernels re-associate it (G = phi^T g, P = Wout G^T / N, out = x + theta P^T + b);

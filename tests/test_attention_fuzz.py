@@ -1,5 +1,5 @@
 """Differential tests of the data-dependent attention path, entry point by entry point: glsdet_attn_split, glsdet_rowsplit,
-glsdet_scale_by_map, glsdet_gate (glsdet_amd/csrc/adapt.hip), glsdet_nonlocal_split (misc.hip, nl_window),
+glsdet_scale_by_map, glsdet_gate (glsdet_amd/csrc/adapt.hip), glsdet_nonlocal_split (nonlocal.hip, nl_window),
 glsdet_dwconv2d_dilated (dwconv.hip) and glsdet_channel_maxmean, in both engine dtypes.
 
 Decisions and copies are compared EXACTLY with the naive reference of tests/attention_reference.py: the split on dyadic

@@ -1,4 +1,4 @@
-"""Bit-exact tests of the non-local block kernels (nl_gram / nl_fold / nl_apply / nl_window, glsdet_amd/csrc/misc.hip) behind
+"""Bit-exact tests of the non-local block kernels (nl_gram / nl_fold / nl_apply / nl_window, glsdet_amd/csrc/nonlocal.hip) behind
 glsdet_nonlocal, glsdet_nonlocal_multi, glsdet_nonlocal_split and torch.ops.glsdet.nonlocal_dot, against
 tests/nonlocal_reference.py.
 
