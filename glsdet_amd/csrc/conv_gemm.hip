@@ -594,7 +594,9 @@ static int launch_gemm1(const ConvArgs& a, hipStream_t st, bool dry) {
   const int np = (kbytes + 127) / 128;
   if (np > 4) return 1;                                                    // K <= 512 bytes: everything at once
   const int lds = np * (CO_T + PX_T) * 128 + (a.res ? gemm_res_bytes<TO>(CO_T, PX_T) : 0);
-  if (a.res && !span_fits_32bit<TO>(a, a.r_sn, a.r_sh, a.r_sw)) return 1;
+  // the residual DMAs take 32-bit offsets; y is stored through 64-bit ones here, but the family keeps ONE documented limit
+  // (include/glsdet_hip.h: y and res spans below 2^31 - 1 bytes), so a hint of it never depends on which variant it names
+  if ((a.res && !span_fits_32bit<TO>(a, a.r_sn, a.r_sh, a.r_sw)) || !span_fits_32bit<TO>(a, a.y_sn, a.y_sh, a.y_sw)) return 1;
   if (dry) return 0;
   ConvArgs b = a;
   if (const char* e = getenv("GLSDET_GEMM_DBG")) b.dbg = atoi(e);          // timing knock-outs (results are then invalid)

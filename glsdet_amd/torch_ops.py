@@ -9,6 +9,9 @@ allocated by the op on the input's device, nothing synchronises.  There is no CP
         x NHWC [N,H,W,C] (C % 8 == 0) fp16 or fp32; w = pack_conv_weight(...) ; scale / bias fp32 [cout_pad];
         y NHWC [N,Ho,Wo,ceil8(cout)];  act: 0 none 1 silu 2 relu 3 lrelu 4 gelu 5 sigmoid (| 0x100 residual first)
         reference: BaseConv drone/models/base/baseConv.py:6-19 (+ Bottleneck add, darknet.py:61-62)
+        limit: the conv reads x through 32-bit descriptor offsets counted from the start of x's STORAGE, so an x whose
+        storage is 2 GiB or more (2^31 - 1 bytes) is refused ("exceeds the 2 GiB descriptor range") even when x itself is
+        a small slice of it, e.g. one image of a large batch tensor: clone() the slice first
     glsdet::conv2d_grouped(x, w, scale, bias, groups, stride, act) -> y
         grouped 3x3 conv, pad 1, stride 1 / 2, C = groups * Cg with Cg in 4 / 8 / 16 / 32; w, scale, bias =
         pack_conv_grouped_weight(...); y NHWC [N,Ho,Wo,C] in x's dtype

@@ -66,7 +66,22 @@ enum {
   GLSDET_E_CAPACITY = -5  /* workspace too small                                    */
 };
 
-/* NHWC view.  Strides in ELEMENTS of `dtype`; channel stride is 1. */
+/* NHWC view.  Strides in ELEMENTS of `dtype`; channel stride is 1.
+ * Addressing range.  Strides are 64-bit and every entry point addresses through them at full width: a view may lie, and
+ * its images may be, more than 2^31 (and 2^32) bytes away from alloc_lo and from each other (tests/test_far_addresses.py).
+ * The exceptions, all refused on the host before any launch:
+ *   - the INPUT of the conv family (glsdet_conv2d, _multi, _chain, glsdet_bottleneck, glsdet_conv2d_gnstats,
+ *     glsdet_csp_fused) is read through 32-bit buffer-descriptor offsets counted from alloc_lo: its ALLOCATION
+ *     (alloc_hi - alloc_lo) must be below 2^31 - 1 bytes, else GLSDET_E_ARG "... exceeds the 2 GiB descriptor range".
+ *     The limit is counted on the allocation, not on the view: one image sliced out of a batch tensor of 2 GiB or more is
+ *     refused although the view is small.  glsdet_csp_fused applies the same limit to the allocation of y.
+ *   - the persistent 1x1 variants (tile_hint 16 .. 31) read res, and 16 .. 28 also store y, through 32-bit offsets from
+ *     the view's base (29 .. 31 store y through 64-bit ones, but the family keeps ONE limit): the SPAN of y and of res
+ *     (bytes from the first to the last element of the view) must be below 2^31 - 1, else the hint "does not apply";
+ *     tile_hint 0 then chooses another kernel, 1 is the generic kernel, both take any span.
+ *   - glsdet_conv2d_grouped, glsdet_csp_fused, glsdet_bottleneck, glsdet_layernorm, glsdet_patch_merge and
+ *     glsdet_window_attention decide "y overlaps x" on the spans of the two views, so two views whose images interleave
+ *     (image strides far larger than an image) are refused as overlapping.                                          */
 typedef struct glsdet_view {
   void*   base;            /* address of element (n=0,h=0,w=0,c=0)                    */
   int64_t sn, sh, sw;      /* element strides                                         */
@@ -191,7 +206,8 @@ int     glsdet_bottleneck_tune(const glsdet_conv_desc* c1, const glsdet_conv_des
  * four-launch form stores it, every product in the k order of the stand-alone kernels: y equals four glsdet_conv2d bit
  * for bit.  Limits: fp16 x and y, x.c == y.c == 64 (hidden 32, ONE Bottleneck), any n / h / w and view strides; y must
  * not overlap x other than as a disjoint channel slice of the same pixel-interleaved buffer.  Anything else is refused
- * with a negative code before any launch (callers fall back to the separate launches).
+ * with a negative code before any launch (callers fall back to the separate launches).  x AND y are addressed through
+ * 32-bit descriptor offsets: the allocation of each (alloc_hi - alloc_lo, not the view) must be below 2^31 - 1 bytes.
  * hint 0 / 1: 8 x 16 / 4 x 16 pixel tiles.                                                                              */
 typedef struct glsdet_csp_desc {
   glsdet_view x, y;
