@@ -184,129 +184,80 @@ __global__ __launch_bounds__(256) void gate_kernel(const unsigned char* a, long 
   }
 }
 
-static inline unsigned grid_of(long items) {
-  long g = (items + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
-
 }  // namespace glsdet
 
 using namespace glsdet;
 
 extern "C" int glsdet_attn_split(const glsdet_view* att, int32_t* split, void* stream) {
-  if (!att || !split) GLS_FAIL(GLSDET_E_ARG, "attn_split: null argument");
-  int rc;
-  if ((rc = check_view(*att, "attn_split.att", false))) return rc;
+  if (int rc = check_views("attn_split: null argument", !split, {{att, "attn_split.att", false}})) return rc;
   if (att->h < 8 || att->w < 8 || att->n < 1 || att->n > 16) GLS_FAIL(GLSDET_E_ARG, "attn_split: needs 1..16 images of at least 8 x 8");
   const size_t lds = (size_t)(att->n * (att->h + 2 * att->w) + 2048) * 4;
   if (lds > 60 * 1024) GLS_FAIL(GLSDET_E_ARG, "attn_split: map too large for one workgroup's sums");
   const glsdet_view a = *att;
-  OpRecord op;
-  op.kind = 2;
-  op.flops = 0;
-  op.bytes = 3.0 * a.n * a.h * a.w * dtype_size(a.dtype);
-  op.name = "attn_split(threshold + centroids)";
-  op.launch = [=](hipStream_t st) -> int {
-    if (a.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(attn_split_kernel<f16>, dim3(1), dim3(1024), lds, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, a.n, a.h, a.w, split);
-    else
-      hipLaunchKernelGGL(attn_split_kernel<float>, dim3(1), dim3(1024), lds, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, a.n, a.h, a.w, split);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  return submit_op(make_op(2, 0, 3.0 * a.n * a.h * a.w * dtype_size(a.dtype), "attn_split(threshold + centroids)"), stream, [=](hipStream_t st) {
+    with_dtype(a.dtype, [&](auto t) {
+      hipLaunchKernelGGL(attn_split_kernel<decltype(t)>, dim3(1), dim3(1024), lds, st, GLS_VIN(a), a.n, a.h, a.w, split);
+    });
+  });
 }
 
 extern "C" int glsdet_rowsplit(const glsdet_view* a, const glsdet_view* b, const glsdet_view* y, const int32_t* split, int32_t mode,
                                void* stream) {
   const int q = (mode >> 4) & 3, shift = (mode >> 8) & 1;
   mode &= 15;
-  if (!a || !y || !split || mode < 0 || mode > 4 || (mode == 2 && !b)) GLS_FAIL(GLSDET_E_ARG, "rowsplit: bad argument");
-  int rc;
-  if ((rc = check_view(*a, "rowsplit.a"))) return rc;
-  if ((rc = check_view(*y, "rowsplit.y"))) return rc;
+  if (int rc = check_views("rowsplit: bad argument", !split || mode < 0 || mode > 4 || (mode == 2 && !b), {{a, "rowsplit.a"}, {y, "rowsplit.y"}}))
+    return rc;
   if (!same_extent(*a, *y) || a->dtype != y->dtype) GLS_FAIL(GLSDET_E_ARG, "rowsplit: a / y mismatch");
   glsdet_view vb = *a;
   if (mode == 2) {
-    if ((rc = check_view(*b, "rowsplit.b"))) return rc;
+    if (int rc = check_view(*b, "rowsplit.b")) return rc;
     if (!same_extent(*b, *y) || b->dtype != y->dtype) GLS_FAIL(GLSDET_E_ARG, "rowsplit: b / y mismatch");
     vb = *b;
   }
   const glsdet_view va = *a, vy = *y;
-  OpRecord op;
-  op.kind = 3;
-  op.flops = 0;
-  op.bytes = 2.0 * va.n * va.h * va.w * va.c * dtype_size(va.dtype);
-  op.name = mode == 2 ? "rowsplit(select)" : (mode == 4 ? "rowsplit(merge quadrant)" : "rowsplit(mask)");
-  op.launch = [=](hipStream_t st) -> int {
+  const char* name = mode == 2 ? "rowsplit(select)" : (mode == 4 ? "rowsplit(merge quadrant)" : "rowsplit(mask)");
+  return submit_op(make_op(3, 0, 2.0 * va.n * va.h * va.w * va.c * dtype_size(va.dtype), name), stream, [=](hipStream_t st) {
     const int vn = 16 / dtype_size(va.dtype);
-    const unsigned g = grid_of((long)va.n * va.h * va.w * (va.c / vn));
-    if (va.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(rowsplit_kernel<f16>, dim3(g), dim3(256), 0, st, (const unsigned char*)va.base, va.sn, va.sh, va.sw, (const unsigned char*)vb.base, vb.sn, vb.sh, vb.sw, (unsigned char*)vy.base, vy.sn, vy.sh, vy.sw, va.n, va.h, va.w, va.c / vn, split, mode, q, shift);
-    else
-      hipLaunchKernelGGL(rowsplit_kernel<float>, dim3(g), dim3(256), 0, st, (const unsigned char*)va.base, va.sn, va.sh, va.sw, (const unsigned char*)vb.base, vb.sn, vb.sh, vb.sw, (unsigned char*)vy.base, vy.sn, vy.sh, vy.sw, va.n, va.h, va.w, va.c / vn, split, mode, q, shift);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+    const unsigned g = grid_1d((long)va.n * va.h * va.w * (va.c / vn));
+    with_dtype(va.dtype, [&](auto t) {
+      hipLaunchKernelGGL(rowsplit_kernel<decltype(t)>, dim3(g), dim3(256), 0, st, GLS_VIN(va), GLS_VIN(vb), GLS_VOUT(vy), va.n, va.h, va.w, va.c / vn, split, mode, q, shift);
+    });
+  });
 }
 
 extern "C" int glsdet_scale_by_map(const glsdet_view* x, const glsdet_view* map, const glsdet_view* y, void* stream) {
-  if (!x || !map || !y) GLS_FAIL(GLSDET_E_ARG, "scale_by_map: null argument");
-  int rc;
-  if ((rc = check_view(*x, "scale_by_map.x"))) return rc;
-  if ((rc = check_view(*map, "scale_by_map.map", false))) return rc;
-  if ((rc = check_view(*y, "scale_by_map.y"))) return rc;
+  if (int rc = check_views("scale_by_map: null argument", false, {{x, "scale_by_map.x"}, {map, "scale_by_map.map", false}, {y, "scale_by_map.y"}}))
+    return rc;
   if (!same_extent(*x, *y) || x->dtype != y->dtype || map->dtype != x->dtype || map->n != x->n || map->h != x->h || map->w != x->w)
     GLS_FAIL(GLSDET_E_ARG, "scale_by_map: extent / dtype mismatch");
   const glsdet_view vx = *x, vm = *map, vy = *y;
-  OpRecord op;
-  op.kind = 3;
-  op.flops = 0;
-  op.bytes = 2.0 * vx.n * vx.h * vx.w * vx.c * dtype_size(vx.dtype);
-  op.name = "scale_by_map";
-  op.launch = [=](hipStream_t st) -> int {
+  return submit_op(make_op(3, 0, 2.0 * vx.n * vx.h * vx.w * vx.c * dtype_size(vx.dtype), "scale_by_map"), stream, [=](hipStream_t st) {
     const int vn = 16 / dtype_size(vx.dtype);
-    const unsigned g = grid_of((long)vx.n * vx.h * vx.w * (vx.c / vn));
-    if (vx.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(scale_by_map_kernel<f16>, dim3(g), dim3(256), 0, st, (const unsigned char*)vx.base, vx.sn, vx.sh, vx.sw, (const unsigned char*)vm.base, vm.sn, vm.sh, vm.sw, (unsigned char*)vy.base, vy.sn, vy.sh, vy.sw, vx.n, vx.h, vx.w, vx.c / vn);
-    else
-      hipLaunchKernelGGL(scale_by_map_kernel<float>, dim3(g), dim3(256), 0, st, (const unsigned char*)vx.base, vx.sn, vx.sh, vx.sw, (const unsigned char*)vm.base, vm.sn, vm.sh, vm.sw, (unsigned char*)vy.base, vy.sn, vy.sh, vy.sw, vx.n, vx.h, vx.w, vx.c / vn);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+    const unsigned g = grid_1d((long)vx.n * vx.h * vx.w * (vx.c / vn));
+    with_dtype(vx.dtype, [&](auto t) {
+      hipLaunchKernelGGL(scale_by_map_kernel<decltype(t)>, dim3(g), dim3(256), 0, st, GLS_VIN(vx), GLS_VIN(vm), GLS_VOUT(vy), vx.n, vx.h, vx.w, vx.c / vn);
+    });
+  });
 }
 
 extern "C" int glsdet_gate(const glsdet_view* a, const glsdet_view* b, const glsdet_view* map, const glsdet_view* y, int32_t mode,
                            void* stream) {
-  if (!a || !b || !y || mode < 0 || mode > 1 || (mode == 0 && !map)) GLS_FAIL(GLSDET_E_ARG, "gate: bad argument");
-  int rc;
-  if ((rc = check_view(*a, "gate.a"))) return rc;
-  if ((rc = check_view(*b, "gate.b"))) return rc;
-  if ((rc = check_view(*y, "gate.y"))) return rc;
+  if (int rc = check_views("gate: bad argument", mode < 0 || mode > 1 || (mode == 0 && !map), {{a, "gate.a"}, {b, "gate.b"}, {y, "gate.y"}}))
+    return rc;
   if (!same_extent(*a, *y) || !same_extent(*b, *y) || a->dtype != y->dtype || b->dtype != y->dtype) GLS_FAIL(GLSDET_E_ARG, "gate: a / b / y mismatch");
   glsdet_view vm = *a;
   if (mode == 0) {
-    if ((rc = check_view(*map, "gate.map", false))) return rc;
+    if (int rc = check_view(*map, "gate.map", false)) return rc;
     if (map->n != y->n || map->h != y->h || map->w != y->w || map->c < 2 || map->dtype != y->dtype) GLS_FAIL(GLSDET_E_ARG, "gate: map must be [n,h,w,>=2] of y's dtype");
     vm = *map;
   }
   const glsdet_view va = *a, vb = *b, vy = *y;
-  OpRecord op;
-  op.kind = 3;
-  op.flops = 0;
-  op.bytes = 3.0 * va.n * va.h * va.w * va.c * dtype_size(va.dtype);
-  op.name = mode == 0 ? "gate(a * m0 + b * m1)" : "gate(a * b)";
-  op.launch = [=](hipStream_t st) -> int {
+  const char* name = mode == 0 ? "gate(a * m0 + b * m1)" : "gate(a * b)";
+  return submit_op(make_op(3, 0, 3.0 * va.n * va.h * va.w * va.c * dtype_size(va.dtype), name), stream, [=](hipStream_t st) {
     const int vn = 16 / dtype_size(va.dtype);
-    const unsigned g = grid_of((long)va.n * va.h * va.w * (va.c / vn));
-    if (va.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(gate_kernel<f16>, dim3(g), dim3(256), 0, st, (const unsigned char*)va.base, va.sn, va.sh, va.sw, (const unsigned char*)vb.base, vb.sn, vb.sh, vb.sw, (const unsigned char*)vm.base, vm.sn, vm.sh, vm.sw, (unsigned char*)vy.base, vy.sn, vy.sh, vy.sw, va.n, va.h, va.w, va.c / vn, mode);
-    else
-      hipLaunchKernelGGL(gate_kernel<float>, dim3(g), dim3(256), 0, st, (const unsigned char*)va.base, va.sn, va.sh, va.sw, (const unsigned char*)vb.base, vb.sn, vb.sh, vb.sw, (const unsigned char*)vm.base, vm.sn, vm.sh, vm.sw, (unsigned char*)vy.base, vy.sn, vy.sh, vy.sw, va.n, va.h, va.w, va.c / vn, mode);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+    const unsigned g = grid_1d((long)va.n * va.h * va.w * (va.c / vn));
+    with_dtype(va.dtype, [&](auto t) {
+      hipLaunchKernelGGL(gate_kernel<decltype(t)>, dim3(g), dim3(256), 0, st, GLS_VIN(va), GLS_VIN(vb), GLS_VIN(vm), GLS_VOUT(vy), va.n, va.h, va.w, va.c / vn, mode);
+    });
+  });
 }

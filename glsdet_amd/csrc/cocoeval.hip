@@ -191,11 +191,7 @@ extern "C" int glsdet_coco_match(const double* dt_box, const double* dt_area, co
   a.P = n_pairs; a.A = n_area; a.T = n_thr; a.ND = n_dt; a.NG = n_gt;
   a.ious = ious; a.gt_order = gt_order; a.gt_ignore = gt_ignore; a.n_regular = n_regular;
   a.dt_match = dt_match; a.dt_ignore = dt_ignore; a.gt_match = gt_match;
-  OpRecord op;
-  op.kind = 6;
-  op.flops = 0;
-  op.bytes = 40.0 * n_dt + 41.0 * n_gt;
-  op.name = "coco_match(iou+order+match)";
+  OpRecord op = make_op(6, 0, 40.0 * n_dt + 41.0 * n_gt, "coco_match(iou+order+match)");
   op.launch = [=](hipStream_t st) -> int {
     const unsigned gp = (unsigned)(a.P < 65535 ? a.P : 65535);
     hipLaunchKernelGGL(coco_iou_kernel, dim3(gp), dim3(256), 0, st, a);

@@ -1053,17 +1053,9 @@ static int build_bneck_op(const glsdet_conv_desc* c1, const glsdet_conv_desc* c2
     GLS_FAIL(GLSDET_E_ARG, "bottleneck: c1.y and c2.x must describe the same hidden tensor");
   if (c1->x.dtype != m1.dtype || c2->y.dtype != m1.dtype) GLS_FAIL(GLSDET_E_ARG, "bottleneck: x, the hidden tensor and y share one dtype");
   // in place is impossible: a workgroup reads the halo of x while its neighbours store their tiles of y
-  const char *xlo = (const char*)c1->x.base, *ylo = (const char*)c2->y.base;
-  const int es = dtype_size(m1.dtype);
-  const int64_t xspan = ((int64_t)(c1->x.n - 1) * c1->x.sn + (int64_t)(c1->x.h - 1) * c1->x.sh + (int64_t)(c1->x.w - 1) * c1->x.sw + c1->x.c) * es;
-  const int64_t yspan = ((int64_t)(c2->y.n - 1) * c2->y.sn + (int64_t)(c2->y.h - 1) * c2->y.sh + (int64_t)(c2->y.w - 1) * c2->y.sw + c2->y.c) * es;
-  if (xlo < ylo + yspan && ylo < xlo + xspan) {
-    // overlapping address ranges are fine only for disjoint channel slices of one pixel-interleaved buffer
-    const bool same_geom = c1->x.sn == c2->y.sn && c1->x.sh == c2->y.sh && c1->x.sw == c2->y.sw;
-    const int64_t d = (ylo - xlo) / es, sw = c1->x.sw;
-    const bool disjoint = same_geom && (d > 0 ? (d >= c1->x.c && d + c2->y.c <= sw) : (d < 0 && -d >= c2->y.c && -d + c1->x.c <= sw));
-    if (!disjoint) GLS_FAIL(GLSDET_E_ARG, "bottleneck: y overlaps x (the fused form cannot run in place)");
-  }
+  // (overlapping address ranges are fine only for disjoint channel slices of one pixel-interleaved buffer)
+  if (views_overlap(c1->x, c2->y) && !channel_slices_disjoint(c1->x, c2->y))
+    GLS_FAIL(GLSDET_E_ARG, "bottleneck: y overlaps x (the fused form cannot run in place)");
   ConvArgs& a = b.c;
   a.x = a1.x; a.x_sn = a1.x_sn; a.x_sh = a1.x_sh; a.x_sw = a1.x_sw;
   a.x_lo = a1.x_lo; a.x_off = a1.x_off; a.x_bytes = a1.x_bytes; a.x_lin = 0;
@@ -1072,7 +1064,7 @@ static int build_bneck_op(const glsdet_conv_desc* c1, const glsdet_conv_desc* c2
   if (glsdet_conv_cout_pad(m1.c) != m1.c) GLS_FAIL(GLSDET_E_ARG, "bottleneck: hidden channels must be a multiple of 32");
   op.kind = 0;
   op.flops = f1 + f2;
-  op.bytes = b1 + b2 - 2.0 * (double)a.M * m1.c * es;      // the hidden tensor is neither written nor read
+  op.bytes = b1 + b2 - 2.0 * (double)a.M * m1.c * dtype_size(m1.dtype);    // the hidden tensor is neither written nor read
   if (conv_bneck_try(b, m1.dtype, hint, &op)) GLS_FAIL(GLSDET_E_ARG, "bottleneck: the fused kernel does not apply to this problem");
   return 0;
 }

@@ -251,8 +251,7 @@ int conv1x1_ws_try(const ConvArgs& a, int xdt, int ydt, OpRecord* op) {
   snprintf(nm, sizeof nm, "conv1x1_ws<%s,%dx64> cin%d cout%d", xdt ? "f32" : "f16", co_t, a.Cin, a.Cout);
   op->name = nm;
   op->launch = [a, co_t, xdt](hipStream_t st) -> int {
-    if (xdt == GLSDET_F16) return co_t == 128 ? launch_ws<f16, 128>(a, st) : launch_ws<f16, 64>(a, st);
-    return co_t == 128 ? launch_ws<float, 128>(a, st) : launch_ws<float, 64>(a, st);
+    return with_dtype(xdt, [&](auto t) { return co_t == 128 ? launch_ws<decltype(t), 128>(a, st) : launch_ws<decltype(t), 64>(a, st); });
   };
   return 0;
 }

@@ -763,13 +763,7 @@ inline int refuse_unknown_hint(const TileHint& t, const char* who) {
 
 // runtime value -> template argument: the host dispatchers call generic lambdas with these
 template <int N> using IC = std::integral_constant<int, N>;
-// the (x, y) dtype pairs the conv kernels are compiled for: f(T{}, TO{})
-template <typename F>
-inline int with_conv_types(int xdt, int ydt, F&& f) {
-  if (xdt == GLSDET_F16 && ydt == GLSDET_F16) return f(f16{}, f16{});
-  if (xdt == GLSDET_F16 && ydt == GLSDET_F32) return f(f16{}, float{});
-  return f(float{}, float{});
-}
+// (with_conv_types, the (x, y) dtype pairs the conv kernels are compiled for, sits beside with_dtype in common.h)
 // cout tiles of CO_T rows and flat pixel tiles of PX_T of one problem (generic kernel, conv_gemm.hip)
 template <int CO_T, int PX_T>
 inline void fill_flat_tiles(ConvArgs& b) {

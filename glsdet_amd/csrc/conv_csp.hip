@@ -365,16 +365,8 @@ static int build_csp_op(const glsdet_csp_desc* d, int hint, OpRecord& op) {
   if (xalloc >= 0x7fffffffLL || yalloc >= 0x7fffffffLL)
     GLS_FAIL(GLSDET_E_ARG, "csp_fused: operand allocation of %lld bytes exceeds the 2 GiB descriptor range", (long long)(xalloc > yalloc ? xalloc : yalloc));
   // in place is impossible: a workgroup reads the halo of x while its neighbours store their tiles of y
-  const char *xlo = (const char*)x.base, *ylo = (const char*)y.base;
-  const int64_t xspan = ((int64_t)(x.n - 1) * x.sn + (int64_t)(x.h - 1) * x.sh + (int64_t)(x.w - 1) * x.sw + x.c) * 2;
-  const int64_t yspan = ((int64_t)(y.n - 1) * y.sn + (int64_t)(y.h - 1) * y.sh + (int64_t)(y.w - 1) * y.sw + y.c) * 2;
-  if (xlo < ylo + yspan && ylo < xlo + xspan) {
-    // overlapping address ranges are fine only for disjoint channel slices of one pixel-interleaved buffer
-    const bool same_geom = x.sn == y.sn && x.sh == y.sh && x.sw == y.sw;
-    const int64_t dd = (ylo - xlo) / 2, sw = x.sw;
-    const bool disjoint = same_geom && (dd > 0 ? (dd >= x.c && dd + y.c <= sw) : (dd < 0 && -dd >= y.c && -dd + x.c <= sw));
-    if (!disjoint) GLS_FAIL(GLSDET_E_ARG, "csp_fused: y overlaps x (the fused form cannot run in place)");
-  }
+  // (overlapping address ranges are fine only for disjoint channel slices of one pixel-interleaved buffer)
+  if (views_overlap(x, y) && !channel_slices_disjoint(x, y)) GLS_FAIL(GLSDET_E_ARG, "csp_fused: y overlaps x (the fused form cannot run in place)");
   CspArgs a = {};
   a.x_lo = (const unsigned char*)x.alloc_lo;
   a.x_off = (unsigned)((const char*)x.base - (const char*)x.alloc_lo);

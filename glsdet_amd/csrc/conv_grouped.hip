@@ -152,15 +152,7 @@ static int build_grouped_op(const glsdet_conv_desc* d, int32_t groups, OpRecord&
   if (M <= 0 || M > 0x7fffffffL - 16) GLS_FAIL(GLSDET_E_ARG, "conv2d_grouped: pixel count %ld out of range", M);
   // the kernel keeps no copy of x: a workgroup must not store where another still reads
   const int es = dtype_size(x.dtype);
-  const char *xlo = (const char*)x.base, *ylo = (const char*)y.base;
-  const int64_t xspan = ((int64_t)(x.n - 1) * x.sn + (int64_t)(x.h - 1) * x.sh + (int64_t)(x.w - 1) * x.sw + x.c) * es;
-  const int64_t yspan = ((int64_t)(y.n - 1) * y.sn + (int64_t)(y.h - 1) * y.sh + (int64_t)(y.w - 1) * y.sw + y.c) * es;
-  if (xlo < ylo + yspan && ylo < xlo + xspan) {
-    const bool same_geom = x.sn == y.sn && x.sh == y.sh && x.sw == y.sw;
-    const int64_t off = (ylo - xlo) / es, sw = x.sw;
-    const bool disjoint = same_geom && (off > 0 ? (off >= x.c && off + y.c <= sw) : (off < 0 && -off >= y.c && -off + x.c <= sw));
-    if (!disjoint) GLS_FAIL(GLSDET_E_ARG, "conv2d_grouped: y overlaps x (the conv cannot run in place)");
-  }
+  if (views_overlap(x, y) && !channel_slices_disjoint(x, y)) GLS_FAIL(GLSDET_E_ARG, "conv2d_grouped: y overlaps x (the conv cannot run in place)");
 
   GroupedArgs a;
   a.x = (const unsigned char*)x.base;
@@ -177,19 +169,15 @@ static int build_grouped_op(const glsdet_conv_desc* d, int32_t groups, OpRecord&
   gls_fastdiv(Ho * Wo, &a.howo_mul, &a.howo_sh);
   gls_fastdiv(Wo, &a.wo_mul, &a.wo_sh);
   const int dt = x.dtype, nblk = (x.c + 31) / 32, cg = x.c / groups;
-  op.kind = 0;
-  op.flops = 2.0 * (double)M * x.c * 9 * cg;
-  op.bytes = ((double)x.n * x.h * x.w + (double)M) * x.c * es + (double)nblk * 9 * 32 * 32 * es;
   char nm[112];
   snprintf(nm, sizeof nm, "conv_grouped<%s> 3x3 s%d g%d cg%d blk32x%d", dt ? "f32" : "f16", d->stride, groups, cg, nblk);
-  op.name = nm;
+  op = make_op(0, 2.0 * (double)M * x.c * 9 * cg, ((double)x.n * x.h * x.w + (double)M) * x.c * es + (double)nblk * 9 * 32 * 32 * es, nm);
   op.launch = [a, dt, nblk](hipStream_t st) -> int {
     int gy = (a.ngroups + 3) / 4;
     const int cap = GLS_GROUPED_MAX_WG / nblk > 1 ? GLS_GROUPED_MAX_WG / nblk : 1;
     if (gy > cap) gy = cap;
     const dim3 grid((unsigned)nblk, (unsigned)gy);
-    if (dt == GLSDET_F16) hipLaunchKernelGGL(conv_grouped_kernel<f16>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(conv_grouped_kernel<float>, grid, dim3(256), 0, st, a);
+    with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(conv_grouped_kernel<decltype(t)>, grid, dim3(256), 0, st, a); });
     GLS_HIP(hipGetLastError());
     return 0;
   };

@@ -872,8 +872,7 @@ static int ring8_any(const ConvArgs& a, hipStream_t st) {
 // runtime (element type, cout tile) and tile geometry -> template arguments: f(T{}, IC<CO_T>{}) / f(IC<GEO>{})
 template <typename F>
 static int with_elem_co(int xdt, int co_t, F&& f) {
-  if (xdt == GLSDET_F16) return co_t == 128 ? f(f16{}, IC<128>{}) : f(f16{}, IC<64>{});
-  return co_t == 128 ? f(float{}, IC<128>{}) : f(float{}, IC<64>{});
+  return with_dtype(xdt, [&](auto t) { return co_t == 128 ? f(t, IC<128>{}) : f(t, IC<64>{}); });
 }
 template <typename F>
 static int with_geo(int geo, F&& f) {
@@ -1098,7 +1097,7 @@ int conv_halo_try(const ConvArgs& a, int xdt, int ydt, const TileHint& hint, OpR
     op->launch = [a, xdt, k64, geo](hipStream_t st) -> int {
       return with_geo(geo, [&](auto g) {
         constexpr int G = decltype(g)::value;
-        return xdt == GLSDET_F16 ? halo_ring8_any<f16, G>(a, k64, st) : halo_ring8_any<float, G>(a, k64, st);
+        return with_dtype(xdt, [&](auto t) { return halo_ring8_any<decltype(t), G>(a, k64, st); });
       });
     };
     return 0;

@@ -81,21 +81,11 @@ extern "C" int glsdet_dwconv2d_dilated(const glsdet_conv_desc* d, int32_t dilati
   a.N = x.n; a.H = x.h; a.W = x.w; a.C = x.c; a.Ho = Ho; a.Wo = Wo;
   a.R = d->R; a.S = d->S; a.stride = d->stride; a.pad = d->pad; a.act = d->act; a.dil = dilation;
   const int dt = x.dtype;
-  OpRecord op;
-  op.kind = 0;
-  op.flops = 2.0 * (double)x.n * Ho * Wo * x.c * d->R * d->S;
-  op.bytes = ((double)x.n * x.h * x.w + (double)x.n * Ho * Wo) * x.c * dtype_size(dt);
   char nm[96];
   snprintf(nm, sizeof nm, "dwconv<%s> %dx%d s%d d%d c%d", dt ? "f32" : "f16", d->R, d->S, d->stride, dilation, x.c);
-  op.name = nm;
-  op.launch = [a, dt](hipStream_t st) -> int {
-    const long items = (long)a.N * a.Ho * a.Wo * (a.C / (dt == GLSDET_F16 ? 8 : 4));
-    long g = (items + 255) / 256;
-    if (g > 8192) g = 8192;
-    if (dt == GLSDET_F16) hipLaunchKernelGGL(dwconv_kernel<f16>, dim3((unsigned)g), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(dwconv_kernel<float>, dim3((unsigned)g), dim3(256), 0, st, a);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  OpRecord op = make_op(0, 2.0 * (double)x.n * Ho * Wo * x.c * d->R * d->S, ((double)x.n * x.h * x.w + (double)x.n * Ho * Wo) * x.c * dtype_size(dt), nm);
+  return submit_op(std::move(op), stream, [a, dt](hipStream_t st) {
+    const unsigned g = grid_1d((long)a.N * a.Ho * a.Wo * (a.C / (16 / dtype_size(dt))));
+    with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(dwconv_kernel<decltype(t)>, dim3(g), dim3(256), 0, st, a); });
+  });
 }

@@ -278,9 +278,7 @@ extern "C" int64_t glsdet_lvc_encode_workspace_bytes(int32_t n, int32_t h, int32
 
 extern "C" int glsdet_lvc_encode(const glsdet_view* x, const float* codewords, const float* scale, void* ws, int64_t ws_bytes,
                                  float* E, void* stream) {
-  if (!x || !codewords || !scale || !ws || !E) GLS_FAIL(GLSDET_E_ARG, "lvc_encode: null argument");
-  int rc;
-  if ((rc = check_view(*x, "lvc_encode.x"))) return rc;
+  if (int rc = check_views("lvc_encode: null argument", !codewords || !scale || !ws || !E, {{x, "lvc_encode.x"}})) return rc;
   const int C = x->c;
   if (C < 32 || C % 32 || C > GLS_LVC_MAXC) GLS_FAIL(GLSDET_E_ARG, "lvc_encode: C must be a multiple of 32 in [32, %d], got %d", GLS_LVC_MAXC, C);
   if ((long)x->h * x->w > GLS_LVC_MAXPIX) GLS_FAIL(GLSDET_E_ARG, "lvc_encode: more than 2^24 pixels per image");
@@ -300,24 +298,13 @@ extern "C" int glsdet_lvc_encode(const glsdet_view* x, const float* codewords, c
   a.Sp = a.Ep + (long)a.n * a.nsl * GLS_LVC_K * C;
   const int dt = x->dtype;
   const double N = (double)x->h * x->w;
-  OpRecord op;
-  op.kind = 4;
-  op.flops = (double)a.n * 4.0 * N * GLS_LVC_K * C;
-  op.bytes = (double)a.n * (2.0 * N * C * dtype_size(dt) + 4.0 * GLS_LVC_K * C);
-  op.name = "lvc_encode(logits+softmax+aggregate, fold)";
-  op.launch = [=](hipStream_t st) -> int {
+  OpRecord op = make_op(4, (double)a.n * 4.0 * N * GLS_LVC_K * C, (double)a.n * (2.0 * N * C * dtype_size(dt) + 4.0 * GLS_LVC_K * C),
+                        "lvc_encode(logits+softmax+aggregate, fold)");
+  return submit_op(std::move(op), stream, [=](hipStream_t st) {
     const dim3 g1(a.nsl, a.n, (a.C + 63) / 64);
-    if (dt == GLSDET_F16)
-      hipLaunchKernelGGL(lvc_encode_kernel<f16>, g1, dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL(lvc_encode_kernel<float>, g1, dim3(256), 0, st, a);
-    long g2 = ((long)a.n * GLS_LVC_K * (a.C / 4) + 255) / 256;
-    if (g2 > 4096) g2 = 4096;
-    hipLaunchKernelGGL(lvc_fold_kernel, dim3((unsigned)g2), dim3(256), 0, st, a);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+    with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(lvc_encode_kernel<decltype(t)>, g1, dim3(256), 0, st, a); });
+    hipLaunchKernelGGL(lvc_fold_kernel, dim3(grid_1d((long)a.n * GLS_LVC_K * (a.C / 4), 4096)), dim3(256), 0, st, a);
+  });
 }
 
 extern "C" int glsdet_lvc_gate(const float* E, int32_t n, int32_t C, const float* a_k, const float* b_k, const float* fc_w,
@@ -326,54 +313,33 @@ extern "C" int glsdet_lvc_gate(const float* E, int32_t n, int32_t C, const float
   if (n < 1 || n > 65535) GLS_FAIL(GLSDET_E_ARG, "lvc_gate: 1..65535 images, got %d", n);
   if (C < 32 || C % 32 || C > GLS_LVC_MAXC) GLS_FAIL(GLSDET_E_ARG, "lvc_gate: C must be a multiple of 32 in [32, %d], got %d", GLS_LVC_MAXC, C);
   if (((uintptr_t)E & 15) || ((uintptr_t)fc_w & 15) || ((uintptr_t)gam & 15)) GLS_FAIL(GLSDET_E_ALIGN, "lvc_gate: E / fc_w / gam must be 16-byte aligned");
-  OpRecord op;
-  op.kind = 4;
-  op.flops = (double)n * (2.0 * C * C + 3.0 * GLS_LVC_K * C);
-  op.bytes = (double)n * 4.0 * (GLS_LVC_K * C + C) + 4.0 * C * C;
-  op.name = "lvc_gate(bn1d+relu+mean+fc+sigmoid)";
-  op.launch = [=](hipStream_t st) -> int {
+  OpRecord op = make_op(4, (double)n * (2.0 * C * C + 3.0 * GLS_LVC_K * C), (double)n * 4.0 * (GLS_LVC_K * C + C) + 4.0 * C * C,
+                        "lvc_gate(bn1d+relu+mean+fc+sigmoid)");
+  return submit_op(std::move(op), stream, [=](hipStream_t st) {
     hipLaunchKernelGGL(lvc_gate_kernel, dim3((C + 63) / 64, n), dim3(64), 0, st, E, a_k, b_k, fc_w, fc_b, gam, C);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  });
 }
 
 extern "C" int glsdet_channel_fuse(const glsdet_view* a, const glsdet_view* t, const glsdet_view* y, const float* v, int32_t mode,
                                    void* stream) {
-  if (!a || !y || !v || mode < 0 || mode > 1 || (mode == 1 && !t)) GLS_FAIL(GLSDET_E_ARG, "channel_fuse: bad argument");
-  int rc;
-  if ((rc = check_view(*a, "channel_fuse.a"))) return rc;
-  if ((rc = check_view(*y, "channel_fuse.y"))) return rc;
+  if (int rc = check_views("channel_fuse: bad argument", !v || mode < 0 || mode > 1 || (mode == 1 && !t), {{a, "channel_fuse.a"}, {y, "channel_fuse.y"}}))
+    return rc;
   if (!same_extent(*a, *y) || a->dtype != y->dtype) GLS_FAIL(GLSDET_E_ARG, "channel_fuse: a / y mismatch");
   const int vn = 16 / dtype_size(a->dtype);
   if (a->c % vn) GLS_FAIL(GLSDET_E_ARG, "channel_fuse: channels must be a multiple of %d, got %d", vn, a->c);
   if ((uintptr_t)v & 15) GLS_FAIL(GLSDET_E_ALIGN, "channel_fuse: v must be 16-byte aligned");
   glsdet_view vt = *a;
   if (mode == 1) {
-    if ((rc = check_view(*t, "channel_fuse.t"))) return rc;
+    if (int rc = check_view(*t, "channel_fuse.t")) return rc;
     if (!same_extent(*t, *y) || t->dtype != y->dtype) GLS_FAIL(GLSDET_E_ARG, "channel_fuse: t / y mismatch");
     vt = *t;
   }
   const glsdet_view va = *a, vy = *y;
-  OpRecord op;
-  op.kind = 3;
-  op.flops = 0;
-  op.bytes = (mode == 1 ? 3.0 : 2.0) * va.n * va.h * va.w * va.c * dtype_size(va.dtype);
-  op.name = mode == 0 ? "channel_fuse(relu(a + a * v[n,c]))" : "channel_fuse(a + v[c] * t)";
-  op.launch = [=](hipStream_t st) -> int {
-    long g = ((long)va.n * va.h * va.w * (va.c / vn) + 255) / 256;
-    if (g > 8192) g = 8192;
-    if (va.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(channel_fuse_kernel<f16>, dim3((unsigned)g), dim3(256), 0, st, (const unsigned char*)va.base, va.sn, va.sh, va.sw,
-                         (const unsigned char*)vt.base, vt.sn, vt.sh, vt.sw, (unsigned char*)vy.base, vy.sn, vy.sh, vy.sw, v, va.n, va.h,
-                         va.w, va.c / vn, mode);
-    else
-      hipLaunchKernelGGL(channel_fuse_kernel<float>, dim3((unsigned)g), dim3(256), 0, st, (const unsigned char*)va.base, va.sn, va.sh, va.sw,
-                         (const unsigned char*)vt.base, vt.sn, vt.sh, vt.sw, (unsigned char*)vy.base, vy.sn, vy.sh, vy.sw, v, va.n, va.h,
-                         va.w, va.c / vn, mode);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  const char* name = mode == 0 ? "channel_fuse(relu(a + a * v[n,c]))" : "channel_fuse(a + v[c] * t)";
+  return submit_op(make_op(3, 0, (mode == 1 ? 3.0 : 2.0) * va.n * va.h * va.w * va.c * dtype_size(va.dtype), name), stream, [=](hipStream_t st) {
+    const unsigned g = grid_1d((long)va.n * va.h * va.w * (va.c / vn));
+    with_dtype(va.dtype, [&](auto e) {
+      hipLaunchKernelGGL(channel_fuse_kernel<decltype(e)>, dim3(g), dim3(256), 0, st, GLS_VIN(va), GLS_VIN(vt), GLS_VOUT(vy), v, va.n, va.h, va.w, va.c / vn, mode);
+    });
+  });
 }

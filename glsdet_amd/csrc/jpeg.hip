@@ -256,11 +256,7 @@ extern "C" int glsdet_jpeg_reconstruct(const glsdet_jpeg_desc* d, const int16_t*
     GLS_FAIL(GLSDET_E_ARG, "jpeg_reconstruct: dst_row_bytes %lld is below 3 * width = %d", (long long)dst_row_bytes, 3 * g.width);
   if (order != 0 && order != 1) GLS_FAIL(GLSDET_E_ARG, "jpeg_reconstruct: order %d (0 RGB, 1 BGR)", order);
   unsigned char* planes = (unsigned char*)ws;
-  OpRecord op;
-  op.kind = 1;
-  op.flops = 0;
-  op.bytes = 128.0 * g.n_blocks + 64.0 * g.n_blocks * 2 + 3.0 * g.width * g.height;
-  op.name = "jpeg_idct+upsample_colour";
+  OpRecord op = make_op(1, 0, 128.0 * g.n_blocks + 64.0 * g.n_blocks * 2 + 3.0 * g.width * g.height, "jpeg_idct+upsample_colour");
   op.launch = [=](hipStream_t st) -> int {
     long g1 = (g.n_blocks + 31) / 32, g2 = ((long)g.height * ((g.width + 3) / 4) + 255) / 256;
     if (g1 > GLS_JPEG_GRID_CAP) g1 = GLS_JPEG_GRID_CAP;

@@ -296,183 +296,119 @@ __global__ __launch_bounds__(256) void transpose_many_kernel(CopyManyArgs a) {
   }
 }
 
-static inline unsigned grid_for(long work_items, int block = 256, long cap = 256L * 32) {
-  long g = (work_items + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (unsigned)g;
-}
-
 }  // namespace glsdet
 
 using namespace glsdet;
 
 extern "C" int glsdet_focus_pack(const float* img, int32_t n, int32_t cin, int32_t H, int32_t W,
                                  const glsdet_view* y, void* stream) {
-  if (!img || !y) GLS_FAIL(GLSDET_E_ARG, "focus_pack: null argument");
-  int rc;
-  if ((rc = check_view(*y, "focus_pack.y"))) return rc;
+  if (int rc = check_views("focus_pack: null argument", !img, {{y, "focus_pack.y"}})) return rc;
   if (H % 2 || W % 2 || n < 1 || cin < 1) GLS_FAIL(GLSDET_E_ARG, "focus_pack: H,W must be even");
   if (y->n != n || y->h != H / 2 || y->w != W / 2 || y->c < 4 * cin)
     GLS_FAIL(GLSDET_E_ARG, "focus_pack: output extent mismatch");
   const glsdet_view v = *y;
-  OpRecord op;
-  op.kind = 1;
-  op.flops = 0;
-  op.bytes = (double)n * cin * H * W * 4 + (double)n * (H / 2) * (W / 2) * v.c * dtype_size(v.dtype);
-  op.name = "focus_pack";
-  op.launch = [=](hipStream_t st) -> int {
-    const unsigned g = grid_for((long)n * (H / 2) * (W / 2));
-    if (v.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(focus_pack_kernel<f16>, dim3(g), dim3(256), 0, st, img, n, cin, H, W, (unsigned char*)v.base, v.sn, v.sh, v.sw, v.c);
-    else
-      hipLaunchKernelGGL(focus_pack_kernel<float>, dim3(g), dim3(256), 0, st, img, n, cin, H, W, (unsigned char*)v.base, v.sn, v.sh, v.sw, v.c);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  const double bytes = (double)n * cin * H * W * 4 + (double)n * (H / 2) * (W / 2) * v.c * dtype_size(v.dtype);
+  return submit_op(make_op(1, 0, bytes, "focus_pack"), stream, [=](hipStream_t st) {
+    const unsigned g = grid_1d((long)n * (H / 2) * (W / 2));
+    with_dtype(v.dtype, [&](auto t) {
+      hipLaunchKernelGGL(focus_pack_kernel<decltype(t)>, dim3(g), dim3(256), 0, st, img, n, cin, H, W, GLS_VOUT(v), v.c);
+    });
+  });
 }
 
 extern "C" int glsdet_maxpool2d(const glsdet_view* x, const glsdet_view* y, int32_t k, void* stream) {
-  if (!x || !y) GLS_FAIL(GLSDET_E_ARG, "maxpool2d: null argument");
-  int rc;
-  if ((rc = check_view(*x, "maxpool2d.x"))) return rc;
-  if ((rc = check_view(*y, "maxpool2d.y"))) return rc;
+  if (int rc = check_views("maxpool2d: null argument", false, {{x, "maxpool2d.x"}, {y, "maxpool2d.y"}})) return rc;
   if (!same_extent(*x, *y) || x->dtype != y->dtype) GLS_FAIL(GLSDET_E_ARG, "maxpool2d: x/y extent or dtype mismatch");
   if (k < 1 || !(k & 1) || k > 31) GLS_FAIL(GLSDET_E_ARG, "maxpool2d: k must be odd in [1,31]");
   if (x->c % 8) GLS_FAIL(GLSDET_E_ARG, "maxpool2d: channels must be a multiple of 8");
   const glsdet_view a = *x, b = *y;
-  OpRecord op;
-  op.kind = 2;
-  op.flops = 0;
-  op.bytes = 2.0 * a.n * a.h * a.w * a.c * dtype_size(a.dtype);
-  op.name = "maxpool";
-  op.launch = [=](hipStream_t st) -> int {
+  return submit_op(make_op(2, 0, 2.0 * a.n * a.h * a.w * a.c * dtype_size(a.dtype), "maxpool"), stream, [=](hipStream_t st) {
     const int vn = 16 / dtype_size(a.dtype);
-    const unsigned g = grid_for((long)a.n * a.h * a.w * (a.c / vn));
-    if (a.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(maxpool_kernel<f16>, dim3(g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, (unsigned char*)b.base, b.sn, b.sh, b.sw, a.n, a.h, a.w, a.c, k);
-    else
-      hipLaunchKernelGGL(maxpool_kernel<float>, dim3(g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, (unsigned char*)b.base, b.sn, b.sh, b.sw, a.n, a.h, a.w, a.c, k);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+    const unsigned g = grid_1d((long)a.n * a.h * a.w * (a.c / vn));
+    with_dtype(a.dtype, [&](auto t) {
+      hipLaunchKernelGGL(maxpool_kernel<decltype(t)>, dim3(g), dim3(256), 0, st, GLS_VIN(a), GLS_VOUT(b), a.n, a.h, a.w, a.c, k);
+    });
+  });
 }
 
 extern "C" int glsdet_spp_pools(const glsdet_view* x, const glsdet_view* y5, const glsdet_view* y9, const glsdet_view* y13, void* stream) {
-  if (!x || !y5 || !y9 || !y13) GLS_FAIL(GLSDET_E_ARG, "spp_pools: null argument");
-  int rc;
-  if ((rc = check_view(*x, "spp_pools.x"))) return rc;
-  const glsdet_view* ys[3] = {y5, y9, y13};
-  for (int i = 0; i < 3; ++i) {
-    if ((rc = check_view(*ys[i], "spp_pools.y"))) return rc;
-    if (!same_extent(*x, *ys[i]) || ys[i]->dtype != x->dtype || ys[i]->sn != y5->sn || ys[i]->sh != y5->sh || ys[i]->sw != y5->sw)
+  if (int rc = check_views("spp_pools: null argument", !y5 || !y9 || !y13, {{x, "spp_pools.x"}})) return rc;
+  for (const glsdet_view* yi : {y5, y9, y13}) {
+    if (int rc = check_view(*yi, "spp_pools.y")) return rc;
+    if (!same_extent(*x, *yi) || yi->dtype != x->dtype || yi->sn != y5->sn || yi->sh != y5->sh || yi->sw != y5->sw)
       GLS_FAIL(GLSDET_E_ARG, "spp_pools: outputs must have x's extent and dtype and share one set of strides");
   }
   if (x->c % 8) GLS_FAIL(GLSDET_E_ARG, "spp_pools: channels must be a multiple of 8");
   const glsdet_view a = *x, b5 = *y5, b9 = *y9, b13 = *y13;
-  OpRecord op;
-  op.kind = 2;
-  op.flops = 0;
-  op.bytes = 4.0 * a.n * a.h * a.w * a.c * dtype_size(a.dtype);
-  op.name = "spp_pools(5,9,13)";
-  op.launch = [=](hipStream_t st) -> int {
+  return submit_op(make_op(2, 0, 4.0 * a.n * a.h * a.w * a.c * dtype_size(a.dtype), "spp_pools(5,9,13)"), stream, [=](hipStream_t st) -> int {
     const int vn = 16 / dtype_size(a.dtype);
     const int tiles_x = (a.w + 15) / 16, tiles_y = (a.h + 7) / 8, cch = a.c / vn;
     const long g = (long)a.n * tiles_y * tiles_x * cch;
     if (g <= 0 || g > 0x7fffffffL) GLS_FAIL(GLSDET_E_ARG, "spp_pools: grid out of range");
-    if (a.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(spp_pools_kernel<f16>, dim3((unsigned)g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, (unsigned char*)b5.base, (unsigned char*)b9.base, (unsigned char*)b13.base, b5.sn, b5.sh, b5.sw, a.h, a.w, cch, tiles_x, tiles_y);
-    else
-      hipLaunchKernelGGL(spp_pools_kernel<float>, dim3((unsigned)g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, (unsigned char*)b5.base, (unsigned char*)b9.base, (unsigned char*)b13.base, b5.sn, b5.sh, b5.sw, a.h, a.w, cch, tiles_x, tiles_y);
-    GLS_HIP(hipGetLastError());
+    with_dtype(a.dtype, [&](auto t) {
+      hipLaunchKernelGGL(spp_pools_kernel<decltype(t)>, dim3((unsigned)g), dim3(256), 0, st, GLS_VIN(a), (unsigned char*)b5.base, (unsigned char*)b9.base, (unsigned char*)b13.base, b5.sn, b5.sh, b5.sw, a.h, a.w, cch, tiles_x, tiles_y);
+    });
     return 0;
-  };
-  return submit(std::move(op), stream);
+  });
 }
 
 extern "C" int glsdet_channel_maxmean(const glsdet_view* x, const glsdet_view* y, void* stream) {
-  if (!x || !y) GLS_FAIL(GLSDET_E_ARG, "channel_maxmean: null argument");
-  int rc;
-  if ((rc = check_view(*x, "channel_maxmean.x"))) return rc;
-  if ((rc = check_view(*y, "channel_maxmean.y"))) return rc;
+  if (int rc = check_views("channel_maxmean: null argument", false, {{x, "channel_maxmean.x"}, {y, "channel_maxmean.y"}})) return rc;
   if (x->dtype != y->dtype || y->n != x->n || y->h != x->h || y->w != x->w || y->c != 8 || x->c % 8)
     GLS_FAIL(GLSDET_E_ARG, "channel_maxmean: y must be [n,h,w,8] of x's dtype, x.c a multiple of 8");
   const glsdet_view a = *x, b = *y;
-  OpRecord op;
-  op.kind = 2;
-  op.flops = 0;
-  op.bytes = (double)a.n * a.h * a.w * (a.c + 8) * dtype_size(a.dtype);
-  op.name = "channel_maxmean";
-  op.launch = [=](hipStream_t st) -> int {
-    const unsigned g = grid_for((long)a.n * a.h * a.w * 64);
-    if (a.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(channel_maxmean_kernel<f16>, dim3(g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, (unsigned char*)b.base, b.sn, b.sh, b.sw, a.n, a.h, a.w, a.c);
-    else
-      hipLaunchKernelGGL(channel_maxmean_kernel<float>, dim3(g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, (unsigned char*)b.base, b.sn, b.sh, b.sw, a.n, a.h, a.w, a.c);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  return submit_op(make_op(2, 0, (double)a.n * a.h * a.w * (a.c + 8) * dtype_size(a.dtype), "channel_maxmean"), stream, [=](hipStream_t st) {
+    const unsigned g = grid_1d((long)a.n * a.h * a.w * 64);
+    with_dtype(a.dtype, [&](auto t) {
+      hipLaunchKernelGGL(channel_maxmean_kernel<decltype(t)>, dim3(g), dim3(256), 0, st, GLS_VIN(a), GLS_VOUT(b), a.n, a.h, a.w, a.c);
+    });
+  });
 }
 
 extern "C" int glsdet_resample_copy(const glsdet_view* x, const glsdet_view* y, int32_t factor, void* stream) {
-  if (!x || !y) GLS_FAIL(GLSDET_E_ARG, "resample_copy: null argument");
-  int rc;
-  if ((rc = check_view(*x, "resample_copy.x"))) return rc;
-  if ((rc = check_view(*y, "resample_copy.y"))) return rc;
+  if (int rc = check_views("resample_copy: null argument", false, {{x, "resample_copy.x"}, {y, "resample_copy.y"}})) return rc;
   if (factor < 1 || factor > 8) GLS_FAIL(GLSDET_E_ARG, "resample_copy: bad factor %d", factor);
   if (x->dtype != y->dtype || y->n != x->n || y->c != x->c || y->h != x->h * factor || y->w != x->w * factor)
     GLS_FAIL(GLSDET_E_ARG, "resample_copy: extent mismatch");
   if (x->c % 8) GLS_FAIL(GLSDET_E_ARG, "resample_copy: channels must be a multiple of 8");
   const glsdet_view a = *x, b = *y;
-  OpRecord op;
-  op.kind = 3;
-  op.flops = 0;
-  op.bytes = ((double)a.n * a.h * a.w + (double)b.n * b.h * b.w) * a.c * dtype_size(a.dtype);
-  op.name = factor == 1 ? "copy" : "upsample_nearest";
-  op.launch = [=](hipStream_t st) -> int {
+  const double bytes = ((double)a.n * a.h * a.w + (double)b.n * b.h * b.w) * a.c * dtype_size(a.dtype);
+  return submit_op(make_op(3, 0, bytes, factor == 1 ? "copy" : "upsample_nearest"), stream, [=](hipStream_t st) {
     const int vn = 16 / dtype_size(a.dtype);
-    const unsigned g = grid_for((long)b.n * b.h * b.w * (b.c / vn));
-    if (a.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(resample_kernel<f16>, dim3(g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, (unsigned char*)b.base, b.sn, b.sh, b.sw, b.n, b.h, b.w, b.c, factor);
-    else
-      hipLaunchKernelGGL(resample_kernel<float>, dim3(g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, (unsigned char*)b.base, b.sn, b.sh, b.sw, b.n, b.h, b.w, b.c, factor);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+    const unsigned g = grid_1d((long)b.n * b.h * b.w * (b.c / vn));
+    with_dtype(a.dtype, [&](auto t) {
+      hipLaunchKernelGGL(resample_kernel<decltype(t)>, dim3(g), dim3(256), 0, st, GLS_VIN(a), GLS_VOUT(b), b.n, b.h, b.w, b.c, factor);
+    });
+  });
+}
+
+// the (source, destination) pair i of copy_many / transpose_many as the kernels take it
+static CopyJob copy_job(const glsdet_view& x, const glsdet_view& y) {
+  CopyJob j;
+  j.x = (const unsigned char*)x.base;
+  j.y = (unsigned char*)y.base;
+  j.xsn = x.sn, j.xsh = x.sh, j.xsw = x.sw, j.ysn = y.sn, j.ysh = y.sh, j.ysw = y.sw;
+  j.n = x.n, j.h = x.h, j.w = x.w;
+  return j;
 }
 
 extern "C" int glsdet_copy_many(const glsdet_view* x, const glsdet_view* y, int32_t count, void* stream) {
   if (!x || !y) GLS_FAIL(GLSDET_E_ARG, "copy_many: null argument");
   if (count < 1 || count > 4096) GLS_FAIL(GLSDET_E_ARG, "copy_many: 1..4096 pairs, got %d", count);
-  int rc;
   std::vector<CopyJob> jobs((size_t)count);
   double bytes = 0;
   for (int i = 0; i < count; ++i) {
-    if ((rc = check_view(x[i], "copy_many.x"))) return rc;
-    if ((rc = check_view(y[i], "copy_many.y"))) return rc;
+    if (int rc = check_view(x[i], "copy_many.x")) return rc;
+    if (int rc = check_view(y[i], "copy_many.y")) return rc;
     if (x[i].dtype != x[0].dtype || y[i].dtype != x[0].dtype || x[i].c != x[0].c || y[i].c != x[0].c)
       GLS_FAIL(GLSDET_E_ARG, "copy_many: pair %d: one dtype and one channel count per call", i);
     if (x[i].n != y[i].n || x[i].h != y[i].h || x[i].w != y[i].w) GLS_FAIL(GLSDET_E_ARG, "copy_many: pair %d: extent mismatch", i);
-    CopyJob& j = jobs[(size_t)i];
-    j.x = (const unsigned char*)x[i].base;
-    j.y = (unsigned char*)y[i].base;
-    j.xsn = x[i].sn, j.xsh = x[i].sh, j.xsw = x[i].sw, j.ysn = y[i].sn, j.ysh = y[i].sh, j.ysw = y[i].sw;
-    j.n = x[i].n, j.h = x[i].h, j.w = x[i].w;
-    const long px = (long)j.n * j.h * j.w;
-    bytes += 2.0 * px * x[i].c * dtype_size(x[i].dtype);
+    jobs[(size_t)i] = copy_job(x[i], y[i]);
+    bytes += 2.0 * ((long)x[i].n * x[i].h * x[i].w) * x[i].c * dtype_size(x[i].dtype);
   }
   if (x[0].c % 8) GLS_FAIL(GLSDET_E_ARG, "copy_many: channels must be a multiple of 8");
   const int C = x[0].c, dt = x[0].dtype;
-  OpRecord op;
-  op.kind = 3;
-  op.flops = 0;
-  op.bytes = bytes;
-  op.name = "copy_many[" + std::to_string(count) + "]";
-  op.launch = [=](hipStream_t st) -> int {
+  return submit_op(make_op(3, 0, bytes, "copy_many[" + std::to_string(count) + "]"), stream, [=](hipStream_t st) -> int {
     const int vn = 16 / dtype_size(dt);
     // the pairs share the chip: about four workgroups per CU over one launch, at least one per pair
     for (int j0 = 0; j0 < count; j0 += GLS_COPY_JOBS) {
@@ -484,27 +420,22 @@ extern "C" int glsdet_copy_many(const glsdet_view* x, const glsdet_view* y, int3
         big = std::max(big, (long)a.j[i].n * a.j[i].h * a.j[i].w * (C / vn));
       }
       a.C = C;
-      const unsigned per = (unsigned)std::max(1L, std::min((big + 255) / 256, (long)std::max(1, 2048 / nj)));
-      if (dt == GLSDET_F16)
-        hipLaunchKernelGGL(copy_many_kernel<f16>, dim3(per, nj), dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL(copy_many_kernel<float>, dim3(per, nj), dim3(256), 0, st, a);
+      const unsigned per = grid_1d(big, std::max(1, 2048 / nj));
+      with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(copy_many_kernel<decltype(t)>, dim3(per, nj), dim3(256), 0, st, a); });
       GLS_HIP(hipGetLastError());
     }
     return 0;
-  };
-  return submit(std::move(op), stream);
+  });
 }
 
 extern "C" int glsdet_transpose_many(const glsdet_view* x, const glsdet_view* y, int32_t count, void* stream) {
   if (!x || !y) GLS_FAIL(GLSDET_E_ARG, "transpose_many: null argument");
   if (count < 1 || count > 4096) GLS_FAIL(GLSDET_E_ARG, "transpose_many: 1..4096 pairs, got %d", count);
-  int rc;
   std::vector<CopyJob> jobs((size_t)count);
   double bytes = 0;
   for (int i = 0; i < count; ++i) {
-    if ((rc = check_view(x[i], "transpose_many.x"))) return rc;
-    if ((rc = check_view(y[i], "transpose_many.y"))) return rc;
+    if (int rc = check_view(x[i], "transpose_many.x")) return rc;
+    if (int rc = check_view(y[i], "transpose_many.y")) return rc;
     if (x[i].dtype != x[0].dtype || y[i].dtype != x[0].dtype || x[i].c != x[0].c)
       GLS_FAIL(GLSDET_E_ARG, "transpose_many: pair %d: one dtype and one channel count per call", i);
     const int vn = 16 / dtype_size(x[i].dtype);
@@ -512,21 +443,12 @@ extern "C" int glsdet_transpose_many(const glsdet_view* x, const glsdet_view* y,
     if (x[i].n != 1 || y[i].n != 1 || y[i].h != 1) GLS_FAIL(GLSDET_E_ARG, "transpose_many: pair %d: one image -> one matrix [1,1,rows,cols]", i);
     if (y[i].w < x[i].c || y[i].c < (N + vn - 1) / vn * vn)
       GLS_FAIL(GLSDET_E_ARG, "transpose_many: pair %d: matrix %d x %d too small for %d channels x %ld pixels", i, y[i].w, y[i].c, x[i].c, N);
-    CopyJob& j = jobs[(size_t)i];
-    j.x = (const unsigned char*)x[i].base;
-    j.y = (unsigned char*)y[i].base;
-    j.xsn = x[i].sn, j.xsh = x[i].sh, j.xsw = x[i].sw, j.ysn = y[i].sn, j.ysh = y[i].sh, j.ysw = y[i].sw;
-    j.n = 1, j.h = x[i].h, j.w = x[i].w;
+    jobs[(size_t)i] = copy_job(x[i], y[i]);
     bytes += 2.0 * N * x[i].c * dtype_size(x[i].dtype);
   }
   if (x[0].c % 8) GLS_FAIL(GLSDET_E_ARG, "transpose_many: channels must be a multiple of 8");
   const int C = x[0].c, dt = x[0].dtype;
-  OpRecord op;
-  op.kind = 3;
-  op.flops = 0;
-  op.bytes = bytes;
-  op.name = "transpose_many[" + std::to_string(count) + "]";
-  op.launch = [=](hipStream_t st) -> int {
+  return submit_op(make_op(3, 0, bytes, "transpose_many[" + std::to_string(count) + "]"), stream, [=](hipStream_t st) -> int {
     for (int j0 = 0; j0 < count; j0 += GLS_COPY_JOBS) {
       const int nj = std::min(GLS_COPY_JOBS, count - j0);
       CopyManyArgs a = {};
@@ -537,13 +459,9 @@ extern "C" int glsdet_transpose_many(const glsdet_view* x, const glsdet_view* y,
       }
       a.C = C;
       const dim3 grid((unsigned)((big + 63) / 64), (unsigned)((C + 63) / 64), (unsigned)nj);
-      if (dt == GLSDET_F16)
-        hipLaunchKernelGGL(transpose_many_kernel<f16>, grid, dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL(transpose_many_kernel<float>, grid, dim3(256), 0, st, a);
+      with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(transpose_many_kernel<decltype(t)>, grid, dim3(256), 0, st, a); });
       GLS_HIP(hipGetLastError());
     }
     return 0;
-  };
-  return submit(std::move(op), stream);
+  });
 }

@@ -274,8 +274,9 @@ static int nl_submit(const NlArgs& a, int dt, int maxN, OpRecord&& op, void* str
         g3((maxN + 63) / 64, a.nimg * a.n, (a.cx + GLS_APPLY_CO - 1) / GLS_APPLY_CO);
     const size_t lds2 = (size_t)64 * (a.kc + 1) * 4;
     const size_t lds3 = ((size_t)64 * (a.kc + 1) + (size_t)GLS_APPLY_CO * a.kc) * 4;
-    if (dt == GLSDET_F16) return nl_launch<nl_gram_kernel<f16>, nl_fold_kernel, nl_apply_kernel<f16>>(st, a, g1, g2, g3, lds2, lds3);
-    return nl_launch<nl_gram_kernel<float>, nl_fold_kernel, nl_apply_kernel<float>>(st, a, g1, g2, g3, lds2, lds3);
+    return with_dtype(dt, [&](auto t) {
+      return nl_launch<nl_gram_kernel<decltype(t)>, nl_fold_kernel, nl_apply_kernel<decltype(t)>>(st, a, g1, g2, g3, lds2, lds3);
+    });
   };
   return submit(std::move(op), stream);
 }

@@ -255,8 +255,9 @@ extern "C" int glsdet_nonlocal_mfma(const glsdet_view* x, const glsdet_view* tpg
   op.launch = [=](hipStream_t st) -> int {
     const int nbi = (a.ci + 63) / 64, nbx = (a.cx + 63) / 64;
     const dim3 g1(nbi * nbi, a.nimg, 8 * a.n), g2(a.nimg * a.n, nbx, nbi), g3((maxN + 63) / 64, a.nimg * a.n, nbx);
-    if (dt == GLSDET_F16) return nl_launch<nlm_gram_kernel<f16>, nlm_fold_kernel, nlm_apply_kernel<f16>>(st, a, g1, g2, g3, 0, 0);
-    return nl_launch<nlm_gram_kernel<float>, nlm_fold_kernel, nlm_apply_kernel<float>>(st, a, g1, g2, g3, 0, 0);
+    return with_dtype(dt, [&](auto t) {
+      return nl_launch<nlm_gram_kernel<decltype(t)>, nlm_fold_kernel, nlm_apply_kernel<decltype(t)>>(st, a, g1, g2, g3, 0, 0);
+    });
   };
   return submit(std::move(op), stream);
 }

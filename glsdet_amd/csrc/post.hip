@@ -1009,11 +1009,7 @@ static void launch_greedy_nms(hipStream_t st, int n_img, int max_cand, float thr
 }
 
 // a post-processing op of a plan: no MFMA work, `bytes` of HBM traffic
-static OpRecord post_op(const char* name, double bytes) {
-  OpRecord op;
-  op.kind = 6, op.flops = 0, op.bytes = bytes, op.name = name;
-  return op;
-}
+static OpRecord post_op(const char* name, double bytes) { return make_op(6, 0, bytes, name); }
 
 // The front that glsdet_gfl_detect and glsdet_gfl_candidates (`who`, for the messages) share: the checks of the sizes and
 // of the level views, the views as kernel arguments, the op's HBM bytes (every logit read once), and the launches up to
@@ -1100,20 +1096,10 @@ extern "C" int glsdet_yolox_decode_ex(const glsdet_view* levels, int32_t n_level
   a.out = out;
   a.scale = mode == 1 ? scale_factors : nullptr;
   if (out_elems < (int64_t)a.n * A * (5 + num_classes)) GLS_FAIL(GLSDET_E_CAPACITY, "yolox_decode: output buffer too small");
-  OpRecord op;
-  op.kind = 5;
-  op.flops = 0;
-  op.bytes = (double)a.n * A * (5 + num_classes) * 8.0;
-  op.name = "yolox_decode";
-  op.launch = [a, sigmoid_mask](hipStream_t st) -> int {
-    long g = ((long)a.n * a.A + 255) / 256;
-    if (g > 8192) g = 8192;
+  return submit_op(make_op(5, 0, (double)a.n * A * (5 + num_classes) * 8.0, "yolox_decode"), stream, [a, sigmoid_mask](hipStream_t st) {
     void (*const kern[4])(const DecodeArgs) = {decode_kernel<0>, decode_kernel<1>, decode_kernel<2>, decode_kernel<3>};
-    hipLaunchKernelGGL(kern[sigmoid_mask], dim3((unsigned)g), dim3(256), 0, st, a);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+    hipLaunchKernelGGL(kern[sigmoid_mask], dim3(grid_1d((long)a.n * a.A)), dim3(256), 0, st, a);
+  });
 }
 
 extern "C" int glsdet_yolox_decode(const glsdet_view* levels, int32_t n_levels, int32_t num_classes, int32_t in_h,
@@ -1145,9 +1131,7 @@ extern "C" int glsdet_nms(const float* pred, int32_t n, int32_t A, int32_t num_c
                         (double)n * A * (5 + num_classes) * 4.0);
   op.launch = [=](hipStream_t st) -> int {
     hipLaunchKernelGGL(reset_counters_kernel, dim3(1), dim3(256), 0, st, ws.cnt, 2 * n, status);
-    long g = ((long)n * A + 255) / 256;
-    if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(nms_filter_kernel, dim3((unsigned)g), dim3(256), 0, st, pred, n, A, num_classes, box_mode,
+    hipLaunchKernelGGL(nms_filter_kernel, dim3(grid_1d((long)n * A)), dim3(256), 0, st, pred, n, A, num_classes, box_mode,
                        conf_thres, max_cand, ws, status);
     int fused = 0;
     if (!no_fused) {
@@ -1314,15 +1298,9 @@ extern "C" int glsdet_pack_detections(const float* dets, const int32_t* count, i
                                       float* out, void* stream) {
   if (!dets || !count || !out) GLS_FAIL(GLSDET_E_ARG, "pack_detections: null argument");
   if (n < 1 || max_det < 1 || cap < 1) GLS_FAIL(GLSDET_E_ARG, "pack_detections: bad sizes");
-  OpRecord op = post_op("pack_detections", 2.0 * n * (cap + 1) * 28.0);
-  op.launch = [=](hipStream_t st) -> int {
-    long g = ((long)n * (cap + 1) * 7 + 255) / 256;
-    if (g > 2048) g = 2048;
-    hipLaunchKernelGGL(pack_dets_kernel, dim3((unsigned)g), dim3(256), 0, st, dets, count, n, max_det, cap, out);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  return submit_op(post_op("pack_detections", 2.0 * n * (cap + 1) * 28.0), stream, [=](hipStream_t st) {
+    hipLaunchKernelGGL(pack_dets_kernel, dim3(grid_1d((long)n * (cap + 1) * 7, 2048)), dim3(256), 0, st, dets, count, n, max_det, cap, out);
+  });
 }
 
 extern "C" int64_t glsdet_ufp_merge_workspace_bytes(int32_t max_cand) {
@@ -1345,9 +1323,7 @@ extern "C" int glsdet_ufp_backmap_merge(const float* dets, const int32_t* count,
   op.launch = [=](hipStream_t st) -> int {
     hipLaunchKernelGGL(reset_counters_kernel, dim3(1), dim3(256), 0, st, ws.cnt, 1, status);
     if (n_chips > 0) {
-      long g = ((long)n_chips * max_det + 255) / 256;
-      if (g > 4096) g = 4096;
-      hipLaunchKernelGGL(ufp_backmap_kernel, dim3((unsigned)g), dim3(256), 0, st, dets, count, max_det, chips, n_chips, iof_thr,
+      hipLaunchKernelGGL(ufp_backmap_kernel, dim3(grid_1d((long)n_chips * max_det, 4096)), dim3(256), 0, st, dets, count, max_det, chips, n_chips, iof_thr,
                          max_cand, ws, status);
     }
     launch_greedy_nms(st, 1, max_cand, nms_thr, 1.0f, max_out, ws, out, out_count, 0);

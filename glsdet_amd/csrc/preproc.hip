@@ -102,20 +102,11 @@ extern "C" int glsdet_pil_resize_normalize(const unsigned char* src, int32_t in_
     na.mean[c] = mean3[c];
     na.stdv[c] = std3[c];
   }
-  OpRecord op;
-  op.kind = 1;
-  op.flops = 0;
-  op.bytes = 3.0 * in_h * in_w + 6.0 * in_h * out_w + 12.0 * out_h * out_w;
-  op.name = "pil_bicubic_resize+normalize";
-  op.launch = [=](hipStream_t st) -> int {
-    long g1 = ((long)in_h * out_w + 255) / 256, g2 = ((long)out_h * out_w + 255) / 256;
-    if (g1 > 65535) g1 = 65535;
-    if (g2 > 65535) g2 = 65535;
-    hipLaunchKernelGGL(pil_rows_kernel, dim3((unsigned)g1), dim3(256), 0, st, src, in_h, in_w, xbounds, xkk, xksize, out_w, tmp);
-    hipLaunchKernelGGL(pil_cols_norm_kernel, dim3((unsigned)g2), dim3(256), 0, st, tmp, out_w, ybounds, ykk, yksize, out_h, dst,
+  OpRecord op = make_op(1, 0, 3.0 * in_h * in_w + 6.0 * in_h * out_w + 12.0 * out_h * out_w, "pil_bicubic_resize+normalize");
+  return submit_op(std::move(op), stream, [=](hipStream_t st) {
+    const unsigned g1 = grid_1d((long)in_h * out_w, 65535), g2 = grid_1d((long)out_h * out_w, 65535);
+    hipLaunchKernelGGL(pil_rows_kernel, dim3(g1), dim3(256), 0, st, src, in_h, in_w, xbounds, xkk, xksize, out_w, tmp);
+    hipLaunchKernelGGL(pil_cols_norm_kernel, dim3(g2), dim3(256), 0, st, tmp, out_w, ybounds, ykk, yksize, out_h, dst,
                        (long)dst_h * dst_w, dst_w, off_y, off_x, na);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  });
 }

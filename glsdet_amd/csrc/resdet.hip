@@ -6,25 +6,14 @@
 
 namespace glsdet {
 
-template <typename T> struct V16;
-template <> struct V16<f16> { typedef f16x8 type; static constexpr int N = 8; };
-template <> struct V16<float> { typedef f32x4 type; static constexpr int N = 4; };
-
-static inline unsigned rgrid(long work_items, long cap = 256L * 32) {
-  long g = (work_items + 255) / 256;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (unsigned)g;
-}
-
 // ---------------------------------------------------------------- NCHW fp32 -> NHWC pack
 // One thread per pixel: cin strided float loads (coalesced across the wave along W), the
 // padded pixel leaves as 16-byte stores.
 template <typename T>
 __global__ __launch_bounds__(256) void nchw_pack_kernel(const float* __restrict__ img, int n, int cin, int H, int W,
                                                         unsigned char* y, long sn, long sh, long sw, int cy) {
-  typedef typename V16<T>::type V;
-  constexpr int VN = V16<T>::N;
+  typedef typename Vec16<T>::type V;
+  constexpr int VN = Vec16<T>::N;
   const long total = (long)n * H * W;
   for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     const int w = (int)(p % W);
@@ -46,8 +35,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void pool2d_kernel(const unsigned char* x, long xsn, long xsh, long xsw, int H, int W,
                                                      unsigned char* y, long ysn, long ysh, long ysw, int n, int Ho,
                                                      int Wo, int C, int k, int stride, int pad) {
-  typedef typename V16<T>::type V;
-  constexpr int VN = V16<T>::N;
+  typedef typename Vec16<T>::type V;
+  constexpr int VN = Vec16<T>::N;
   const int cchunks = C / VN;
   const long total = (long)n * Ho * Wo * cchunks;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -81,8 +70,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void upsample_add_kernel(const unsigned char* x, long xsn, long xsh, long xsw, int Hc,
                                                            int Wc, unsigned char* y, long ysn, long ysh, long ysw,
                                                            int n, int H, int W, int C, float scale_h, float scale_w) {
-  typedef typename V16<T>::type V;
-  constexpr int VN = V16<T>::N;
+  typedef typename Vec16<T>::type V;
+  constexpr int VN = Vec16<T>::N;
   const int cchunks = C / VN;
   const long total = (long)n * H * W * cchunks;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -131,8 +120,8 @@ struct GnArgs {
 
 template <typename T>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const GnArgs a) {
-  typedef typename V16<T>::type V;
-  constexpr int VN = V16<T>::N;
+  typedef typename Vec16<T>::type V;
+  constexpr int VN = Vec16<T>::N;
   __shared__ double s_sum[256], s_sq[256];
   const GnSet& S = a.s[blockIdx.z];
   const int b = blockIdx.y, z = blockIdx.x;
@@ -206,8 +195,8 @@ __global__ __launch_bounds__(256) void gn_fold_kernel(const GnArgs a) {
 // 2^-24 |mean * sc| in sh, many ulps of a small sh (and of a small result).
 template <typename T>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const GnArgs a) {
-  typedef typename V16<T>::type V;
-  constexpr int VN = V16<T>::N;
+  typedef typename Vec16<T>::type V;
+  constexpr int VN = Vec16<T>::N;
   __shared__ double s_mean[256], s_rstd[256];
   const GnSet& S = a.s[blockIdx.z];
   if ((int)blockIdx.x >= S.gb) return;
@@ -261,8 +250,8 @@ __global__ __launch_bounds__(256) void proxy_scores_kernel(const unsigned char* 
                                                            const float* dots, long dsn, long dsh, long dsw, float* out,
                                                            long osn, long osh, long osw, int n, int H, int W, int C,
                                                            float gamma, const ProxyArgs a) {
-  typedef typename V16<T>::type V;
-  constexpr int VN = V16<T>::N;
+  typedef typename Vec16<T>::type V;
+  constexpr int VN = Vec16<T>::N;
   const int lane = threadIdx.x & 63, sub = lane & 15, grp = lane >> 4;
   const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
@@ -307,81 +296,47 @@ using namespace glsdet;
 
 extern "C" int glsdet_nchw_pack(const float* img, int32_t n, int32_t cin, int32_t H, int32_t W, const glsdet_view* y,
                                 void* stream) {
-  if (!img || !y) GLS_FAIL(GLSDET_E_ARG, "nchw_pack: null argument");
-  int rc;
-  if ((rc = check_view(*y, "nchw_pack.y"))) return rc;
+  if (int rc = check_views("nchw_pack: null argument", !img, {{y, "nchw_pack.y"}})) return rc;
   if (n < 1 || cin < 1 || y->n != n || y->h != H || y->w != W || y->c < cin || y->c % 8)
     GLS_FAIL(GLSDET_E_ARG, "nchw_pack: y must be [n,H,W,c>=cin], c a multiple of 8");
   const glsdet_view v = *y;
-  OpRecord op;
-  op.kind = 1;
-  op.flops = 0;
-  op.bytes = (double)n * H * W * (cin * 4.0 + v.c * dtype_size(v.dtype));
-  op.name = "nchw_pack";
-  op.launch = [=](hipStream_t st) -> int {
-    const unsigned g = rgrid((long)n * H * W);
-    if (v.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(nchw_pack_kernel<f16>, dim3(g), dim3(256), 0, st, img, n, cin, H, W, (unsigned char*)v.base, v.sn, v.sh, v.sw, v.c);
-    else
-      hipLaunchKernelGGL(nchw_pack_kernel<float>, dim3(g), dim3(256), 0, st, img, n, cin, H, W, (unsigned char*)v.base, v.sn, v.sh, v.sw, v.c);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  return submit_op(make_op(1, 0, (double)n * H * W * (cin * 4.0 + v.c * dtype_size(v.dtype)), "nchw_pack"), stream, [=](hipStream_t st) {
+    const unsigned g = grid_1d((long)n * H * W);
+    with_dtype(v.dtype, [&](auto t) {
+      hipLaunchKernelGGL(nchw_pack_kernel<decltype(t)>, dim3(g), dim3(256), 0, st, img, n, cin, H, W, GLS_VOUT(v), v.c);
+    });
+  });
 }
 
 extern "C" int glsdet_pool2d(const glsdet_view* x, const glsdet_view* y, int32_t k, int32_t stride, int32_t pad,
                              void* stream) {
-  if (!x || !y) GLS_FAIL(GLSDET_E_ARG, "pool2d: null argument");
-  int rc;
-  if ((rc = check_view(*x, "pool2d.x"))) return rc;
-  if ((rc = check_view(*y, "pool2d.y"))) return rc;
+  if (int rc = check_views("pool2d: null argument", false, {{x, "pool2d.x"}, {y, "pool2d.y"}})) return rc;
   if (k < 1 || k > 31 || stride < 1 || pad < 0 || 2 * pad > k) GLS_FAIL(GLSDET_E_ARG, "pool2d: bad k/stride/pad");
   if (x->dtype != y->dtype || x->n != y->n || x->c != y->c || x->c % 8 || y->h != (x->h + 2 * pad - k) / stride + 1 ||
       y->w != (x->w + 2 * pad - k) / stride + 1)
     GLS_FAIL(GLSDET_E_ARG, "pool2d: y must be [n,(h+2p-k)/s+1,(w+2p-k)/s+1,c] of x's dtype");
   const glsdet_view a = *x, b = *y;
-  OpRecord op;
-  op.kind = 2;
-  op.flops = 0;
-  op.bytes = ((double)a.n * a.h * a.w + (double)b.n * b.h * b.w) * a.c * dtype_size(a.dtype);
-  op.name = "pool2d";
-  op.launch = [=](hipStream_t st) -> int {
-    const unsigned g = rgrid((long)b.n * b.h * b.w * (b.c * dtype_size(b.dtype) / 16));
-    if (a.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(pool2d_kernel<f16>, dim3(g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, a.h, a.w, (unsigned char*)b.base, b.sn, b.sh, b.sw, b.n, b.h, b.w, b.c, k, stride, pad);
-    else
-      hipLaunchKernelGGL(pool2d_kernel<float>, dim3(g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, a.h, a.w, (unsigned char*)b.base, b.sn, b.sh, b.sw, b.n, b.h, b.w, b.c, k, stride, pad);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  const double bytes = ((double)a.n * a.h * a.w + (double)b.n * b.h * b.w) * a.c * dtype_size(a.dtype);
+  return submit_op(make_op(2, 0, bytes, "pool2d"), stream, [=](hipStream_t st) {
+    const unsigned g = grid_1d((long)b.n * b.h * b.w * (b.c * dtype_size(b.dtype) / 16));
+    with_dtype(a.dtype, [&](auto t) {
+      hipLaunchKernelGGL(pool2d_kernel<decltype(t)>, dim3(g), dim3(256), 0, st, GLS_VIN(a), a.h, a.w, GLS_VOUT(b), b.n, b.h, b.w, b.c, k, stride, pad);
+    });
+  });
 }
 
 extern "C" int glsdet_upsample_add(const glsdet_view* coarse, const glsdet_view* fine, void* stream) {
-  if (!coarse || !fine) GLS_FAIL(GLSDET_E_ARG, "upsample_add: null argument");
-  int rc;
-  if ((rc = check_view(*coarse, "upsample_add.coarse"))) return rc;
-  if ((rc = check_view(*fine, "upsample_add.fine"))) return rc;
+  if (int rc = check_views("upsample_add: null argument", false, {{coarse, "upsample_add.coarse"}, {fine, "upsample_add.fine"}})) return rc;
   if (coarse->dtype != fine->dtype || coarse->n != fine->n || coarse->c != fine->c || fine->c % 8)
     GLS_FAIL(GLSDET_E_ARG, "upsample_add: n, c, dtype must match; c a multiple of 8");
   const glsdet_view a = *coarse, b = *fine;
-  OpRecord op;
-  op.kind = 3;
-  op.flops = 0;
-  op.bytes = 3.0 * b.n * b.h * b.w * b.c * dtype_size(b.dtype);
-  op.name = "upsample_add";
-  op.launch = [=](hipStream_t st) -> int {
+  return submit_op(make_op(3, 0, 3.0 * b.n * b.h * b.w * b.c * dtype_size(b.dtype), "upsample_add"), stream, [=](hipStream_t st) {
     const float sh = (float)a.h / (float)b.h, sw = (float)a.w / (float)b.w;
-    const unsigned g = rgrid((long)b.n * b.h * b.w * (b.c * dtype_size(b.dtype) / 16));
-    if (a.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(upsample_add_kernel<f16>, dim3(g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, a.h, a.w, (unsigned char*)b.base, b.sn, b.sh, b.sw, b.n, b.h, b.w, b.c, sh, sw);
-    else
-      hipLaunchKernelGGL(upsample_add_kernel<float>, dim3(g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, a.h, a.w, (unsigned char*)b.base, b.sn, b.sh, b.sw, b.n, b.h, b.w, b.c, sh, sw);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+    const unsigned g = grid_1d((long)b.n * b.h * b.w * (b.c * dtype_size(b.dtype) / 16));
+    with_dtype(a.dtype, [&](auto t) {
+      hipLaunchKernelGGL(upsample_add_kernel<decltype(t)>, dim3(g), dim3(256), 0, st, GLS_VIN(a), a.h, a.w, GLS_VOUT(b), b.n, b.h, b.w, b.c, sh, sw);
+    });
+  });
 }
 
 extern "C" int64_t glsdet_groupnorm_workspace_bytes(int32_t n, int32_t groups) {
@@ -408,14 +363,11 @@ static int groupnorm_sets(const glsdet_view* x, const glsdet_view* y, int32_t n_
   const int rows = 256 / (C / vn);
   int max_split = 1, max_gb = 1;
   bool any_stats = false;
-  OpRecord op;
-  op.kind = 7;
-  op.flops = op.bytes = 0;
+  double bytes = 0;
   const long per_set = (long)nimg * GLS_GN_SPLIT * groups * 2 + (long)nimg * groups * 2;      // doubles (the tail holds mean, rstd)
   for (int q = 0; q < n_sets; ++q) {
-    int rc;
-    if ((rc = check_view(x[q], "groupnorm.x"))) return rc;
-    if ((rc = check_view(y[q], "groupnorm.y"))) return rc;
+    if (int rc = check_view(x[q], "groupnorm.x")) return rc;
+    if (int rc = check_view(y[q], "groupnorm.y")) return rc;
     if (!same_extent(x[q], y[q]) || x[q].dtype != dt || y[q].dtype != dt || x[q].c != C || x[q].n != nimg)
       GLS_FAIL(GLSDET_E_ARG, "groupnorm: set %d extent / dtype / channel mismatch", q);
     if (!gamma[q] || !beta[q]) GLS_FAIL(GLSDET_E_ARG, "groupnorm: null gamma/beta");
@@ -444,23 +396,16 @@ static int groupnorm_sets(const glsdet_view* x, const glsdet_view* y, int32_t n_
     if (!S.pre && S.nsplit > max_split) max_split = S.nsplit;
     if (S.gb > max_gb) max_gb = S.gb;
     if (!S.pre) any_stats = true;
-    op.bytes += (S.pre ? 2.0 : 3.0) * nimg * N * C * dtype_size(dt);
+    bytes += (S.pre ? 2.0 : 3.0) * nimg * N * C * dtype_size(dt);
   }
-  op.name = !any_stats ? "groupnorm_multi(apply; stats by the convs)" : (n_sets > 1 ? "groupnorm_multi(stats+apply)" : "groupnorm(stats+apply)");
-  op.launch = [=](hipStream_t st) -> int {
-    if (dt == GLSDET_F16) {
-      if (any_stats) hipLaunchKernelGGL(gn_stats_kernel<f16>, dim3(max_split, nimg, a.n), dim3(256), 0, st, a);
+  const char* name = !any_stats ? "groupnorm_multi(apply; stats by the convs)" : (n_sets > 1 ? "groupnorm_multi(stats+apply)" : "groupnorm(stats+apply)");
+  return submit_op(make_op(7, 0, bytes, name), stream, [=](hipStream_t st) {
+    with_dtype(dt, [&](auto t) {
+      if (any_stats) hipLaunchKernelGGL(gn_stats_kernel<decltype(t)>, dim3(max_split, nimg, a.n), dim3(256), 0, st, a);
       hipLaunchKernelGGL(gn_fold_kernel, dim3(nimg, a.n), dim3(256), 0, st, a);
-      hipLaunchKernelGGL(gn_apply_kernel<f16>, dim3(max_gb, nimg, a.n), dim3(256), 0, st, a);
-    } else {
-      if (any_stats) hipLaunchKernelGGL(gn_stats_kernel<float>, dim3(max_split, nimg, a.n), dim3(256), 0, st, a);
-      hipLaunchKernelGGL(gn_fold_kernel, dim3(nimg, a.n), dim3(256), 0, st, a);
-      hipLaunchKernelGGL(gn_apply_kernel<float>, dim3(max_gb, nimg, a.n), dim3(256), 0, st, a);
-    }
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+      hipLaunchKernelGGL(gn_apply_kernel<decltype(t)>, dim3(max_gb, nimg, a.n), dim3(256), 0, st, a);
+    });
+  });
 }
 
 extern "C" int glsdet_groupnorm_multi(const glsdet_view* x, const glsdet_view* y, int32_t n_sets, int32_t groups,
@@ -481,11 +426,9 @@ extern "C" int glsdet_groupnorm(const glsdet_view* x, const glsdet_view* y, int3
 
 extern "C" int glsdet_proxy_scores(const glsdet_view* feat, const glsdet_view* dots, const int32_t* counts,
                                    int32_t num_classes, float gamma, const glsdet_view* out, void* stream) {
-  if (!feat || !dots || !counts || !out) GLS_FAIL(GLSDET_E_ARG, "proxy_scores: null argument");
-  int rc;
-  if ((rc = check_view(*feat, "proxy_scores.feat"))) return rc;
-  if ((rc = check_view(*dots, "proxy_scores.dots", false))) return rc;
-  if ((rc = check_view(*out, "proxy_scores.out", false))) return rc;
+  if (int rc = check_views("proxy_scores: null argument", !counts,
+                           {{feat, "proxy_scores.feat"}, {dots, "proxy_scores.dots", false}, {out, "proxy_scores.out", false}}))
+    return rc;
   if (dots->dtype != GLSDET_F32 || out->dtype != GLSDET_F32) GLS_FAIL(GLSDET_E_ARG, "proxy_scores: dots/out must be fp32");
   if (num_classes < 1 || num_classes > 256) GLS_FAIL(GLSDET_E_ARG, "proxy_scores: bad num_classes");
   ProxyArgs pa = {};
@@ -505,19 +448,11 @@ extern "C" int glsdet_proxy_scores(const glsdet_view* feat, const glsdet_view* d
       out->n != feat->n || out->h != feat->h || out->w != feat->w || feat->c % 8)
     GLS_FAIL(GLSDET_E_ARG, "proxy_scores: extent mismatch (P=%d)", P);
   const glsdet_view a = *feat, d = *dots, o = *out;
-  OpRecord op;
-  op.kind = 8;
-  op.flops = 0;
-  op.bytes = (double)a.n * a.h * a.w * (a.c * dtype_size(a.dtype) + 4.0 * (P + num_classes));
-  op.name = "proxy_scores";
-  op.launch = [=](hipStream_t st) -> int {
-    const unsigned g = rgrid((long)a.n * a.h * a.w * 16);
-    if (a.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(proxy_scores_kernel<f16>, dim3(g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, (const float*)d.base, d.sn, d.sh, d.sw, (float*)o.base, o.sn, o.sh, o.sw, a.n, a.h, a.w, a.c, gamma, pa);
-    else
-      hipLaunchKernelGGL(proxy_scores_kernel<float>, dim3(g), dim3(256), 0, st, (const unsigned char*)a.base, a.sn, a.sh, a.sw, (const float*)d.base, d.sn, d.sh, d.sw, (float*)o.base, o.sn, o.sh, o.sw, a.n, a.h, a.w, a.c, gamma, pa);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  const double bytes = (double)a.n * a.h * a.w * (a.c * dtype_size(a.dtype) + 4.0 * (P + num_classes));
+  return submit_op(make_op(8, 0, bytes, "proxy_scores"), stream, [=](hipStream_t st) {
+    const unsigned g = grid_1d((long)a.n * a.h * a.w * 16);
+    with_dtype(a.dtype, [&](auto t) {
+      hipLaunchKernelGGL(proxy_scores_kernel<decltype(t)>, dim3(g), dim3(256), 0, st, GLS_VIN(a), (const float*)d.base, d.sn, d.sh, d.sw, (float*)o.base, o.sn, o.sh, o.sw, a.n, a.h, a.w, a.c, gamma, pa);
+    });
+  });
 }

@@ -291,11 +291,7 @@ extern "C" int glsdet_soft_nms(const float* cand, const int32_t* cand_count, int
   a.nt = iou_thr; a.sigma = sigma; a.thresh = min_score;
   const int lds = SNMS_SCRATCH + SNMS_ROW * a.lcap;
   const int block = std::min(1024, (a.lcap + 63) / 64 * 64);
-  OpRecord op;
-  op.kind = 6;
-  op.flops = 0;
-  op.bytes = (double)n * cap * 32.0 + (double)n * max_det * 28.0;
-  op.name = "soft_nms(segment+decay+rank)";
+  OpRecord op = make_op(6, 0, (double)n * cap * 32.0 + (double)n * max_det * 28.0, "soft_nms(segment+decay+rank)");
   op.launch = [=](hipStream_t st) -> int {
     static int attr_lds = 64 * 1024;
     if (lds > attr_lds) {

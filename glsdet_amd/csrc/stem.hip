@@ -761,14 +761,10 @@ extern "C" int glsdet_resnet_stem_pool(const float* img, int32_t n, int32_t cin,
   a.n = n; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.cout = 64; a.act = GLSDET_ACT_RELU;
   a.tiles_x = (Wo + 7) / 8; a.tiles_y = (Ho + 3) / 4; a.strips_x = (a.tiles_x + 5) / 6;
   const int dt = y->dtype;
-  OpRecord op;
-  op.kind = 0;
-  op.flops = 2.0 * (double)n * Hc * Wc * 64 * 147.0;
-  op.bytes = (double)n * 3 * H * W * 4.0 + (double)n * Ho * Wo * 64 * dtype_size(dt);
   char nm[112];
   snprintf(nm, sizeof nm, "resnet_stem_pool<%s> 7x7 s2 cin3 cout64 + relu + maxpool 3x3 s2 (fp32 NCHW image in)", dt ? "f32" : "f16");
-  op.name = nm;
-  op.launch = [a, dt](hipStream_t st) -> int { return dt == GLSDET_F16 ? launch_rstem_pool<f16>(a, st) : launch_rstem_pool<float>(a, st); };
+  OpRecord op = make_op(0, 2.0 * (double)n * Hc * Wc * 64 * 147.0, (double)n * 3 * H * W * 4.0 + (double)n * Ho * Wo * 64 * dtype_size(dt), nm);
+  op.launch = [a, dt](hipStream_t st) -> int { return with_dtype(dt, [&](auto t) { return launch_rstem_pool<decltype(t)>(a, st); }); };
   return submit(std::move(op), stream);
 }
 
@@ -788,14 +784,10 @@ extern "C" int glsdet_resnet_stem(const float* img, int32_t n, int32_t cin, int3
   a.n = n; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.cout = 64; a.act = act;
   a.tiles_x = (Wo + 15) / 16; a.tiles_y = (Ho + 7) / 8; a.strips_x = (a.tiles_x + 5) / 6;
   const int dt = y->dtype;
-  OpRecord op;
-  op.kind = 0;
-  op.flops = 2.0 * (double)n * Ho * Wo * 64 * 147.0;
-  op.bytes = (double)n * 3 * H * W * 4.0 + (double)n * Ho * Wo * 64 * dtype_size(dt);
   char nm[96];
   snprintf(nm, sizeof nm, "resnet_stem<%s,64x8x16> 7x7 s2 cin3 cout64 (fp32 NCHW image in)", dt ? "f32" : "f16");
-  op.name = nm;
-  op.launch = [a, dt](hipStream_t st) -> int { return dt == GLSDET_F16 ? launch_rstem<f16>(a, st) : launch_rstem<float>(a, st); };
+  OpRecord op = make_op(0, 2.0 * (double)n * Ho * Wo * 64 * 147.0, (double)n * 3 * H * W * 4.0 + (double)n * Ho * Wo * 64 * dtype_size(dt), nm);
+  op.launch = [a, dt](hipStream_t st) -> int { return with_dtype(dt, [&](auto t) { return launch_rstem<decltype(t)>(a, st); }); };
   return submit(std::move(op), stream);
 }
 
@@ -826,14 +818,11 @@ extern "C" int glsdet_focus_conv_down(const float* img, int32_t n, int32_t cin, 
   b.img = img; b.w1 = (const unsigned char*)w1; b.scale1 = scale1; b.bias1 = bias1;
   b.IH = H; b.IW = W; b.kpad1 = glsdet_conv_kpad(3, 3, 16, dt); b.act1 = act1;
   a.dbg = getenv("GLSDET_STEM2_DBG") ? atoi(getenv("GLSDET_STEM2_DBG")) : 0;      // knock-out timing experiments (results invalid)
-  OpRecord op;
-  op.kind = 0;
-  op.flops = 2.0 * (double)n * Hs * Ws * 32 * 108.0 + 2.0 * (double)n * Ho * Wo * y->c * 288.0;
-  op.bytes = (double)n * 3 * H * W * 4.0 + (double)n * Ho * Wo * y->c * es;
   char nm[112];
   snprintf(nm, sizeof nm, "focus_stem_down<%s> 3x3 cin12 cout32 -> 3x3 s2 cout%d (fp32 NCHW image in)", dt ? "f32" : "f16", y->c);
-  op.name = nm;
-  op.launch = [b, dt](hipStream_t st) -> int { return dt == GLSDET_F16 ? launch_stem_down<f16>(b, st) : launch_stem_down<float>(b, st); };
+  OpRecord op = make_op(0, 2.0 * (double)n * Hs * Ws * 32 * 108.0 + 2.0 * (double)n * Ho * Wo * y->c * 288.0,
+                        (double)n * 3 * H * W * 4.0 + (double)n * Ho * Wo * y->c * es, nm);
+  op.launch = [b, dt](hipStream_t st) -> int { return with_dtype(dt, [&](auto t) { return launch_stem_down<decltype(t)>(b, st); }); };
   return submit(std::move(op), stream);
 }
 
@@ -853,16 +842,11 @@ extern "C" int glsdet_focus_conv(const float* img, int32_t n, int32_t cin, int32
   a.cout = y->c; a.cout_pad = glsdet_conv_cout_pad(y->c); a.kpad = glsdet_conv_kpad(3, 3, 16, y->dtype); a.act = act;
   a.tiles_x = (a.Wo + 15) / 16; a.tiles_y = (a.Ho + 7) / 8; a.strips_x = (a.tiles_x + 5) / 6;
   const int dt = y->dtype, big = a.cout_pad > 32;
-  OpRecord op;
-  op.kind = 0;
-  op.flops = 2.0 * (double)n * a.Ho * a.Wo * y->c * 108.0;
-  op.bytes = (double)n * 3 * H * W * 4.0 + (double)n * a.Ho * a.Wo * y->c * dtype_size(dt);
   char nm[96];
   snprintf(nm, sizeof nm, "focus_stem<%s,%dx8x16> 3x3 s1 cin12 cout%d (fp32 NCHW image in)", dt ? "f32" : "f16", big ? 64 : 32, y->c);
-  op.name = nm;
+  OpRecord op = make_op(0, 2.0 * (double)n * a.Ho * a.Wo * y->c * 108.0, (double)n * 3 * H * W * 4.0 + (double)n * a.Ho * a.Wo * y->c * dtype_size(dt), nm);
   op.launch = [a, dt, big](hipStream_t st) -> int {
-    if (dt == GLSDET_F16) return big ? launch_stem<f16, 64>(a, st) : launch_stem<f16, 32>(a, st);
-    return big ? launch_stem<float, 64>(a, st) : launch_stem<float, 32>(a, st);
+    return with_dtype(dt, [&](auto t) { return big ? launch_stem<decltype(t), 64>(a, st) : launch_stem<decltype(t), 32>(a, st); });
   };
   return submit(std::move(op), stream);
 }

@@ -40,18 +40,6 @@ namespace glsdet {
 #define GLS_WIN_MAXC 1024
 #define GLS_WIN_MAXGRID 4096     // workgroups of one (window, head) item at a time
 
-// [lo, hi) in bytes of everything a view can address
-static inline void view_span(const glsdet_view& v, const char** lo, const char** hi) {
-  *lo = (const char*)v.base;
-  *hi = *lo + ((int64_t)(v.n - 1) * v.sn + (int64_t)(v.h - 1) * v.sh + (int64_t)(v.w - 1) * v.sw + v.c) * dtype_size(v.dtype);
-}
-static inline bool views_overlap(const glsdet_view& a, const glsdet_view& b) {
-  const char *alo, *ahi, *blo, *bhi;
-  view_span(a, &alo, &ahi);
-  view_span(b, &blo, &bhi);
-  return alo < bhi && blo < ahi;
-}
-
 struct LnArgs {
   const unsigned char* x;
   long xsn, xsh, xsw;
@@ -314,10 +302,7 @@ using namespace glsdet;
 
 extern "C" int glsdet_layernorm(const glsdet_view* x, const glsdet_view* y, const float* gamma, const float* beta, float eps,
                                 void* stream) {
-  if (!x || !y || !gamma || !beta) GLS_FAIL(GLSDET_E_ARG, "layernorm: null argument");
-  int rc;
-  if ((rc = check_view(*x, "layernorm.x"))) return rc;
-  if ((rc = check_view(*y, "layernorm.y"))) return rc;
+  if (int rc = check_views("layernorm: null argument", !gamma || !beta, {{x, "layernorm.x"}, {y, "layernorm.y"}})) return rc;
   if (!same_extent(*x, *y)) GLS_FAIL(GLSDET_E_ARG, "layernorm: x / y extents differ");
   const int C = x->c;
   if (C < 32 || C % 32 || C > GLS_LN_MAXC) GLS_FAIL(GLSDET_E_ARG, "layernorm: C must be a multiple of 32 in [32, %d], got %d", GLS_LN_MAXC, C);
@@ -333,34 +318,20 @@ extern "C" int glsdet_layernorm(const glsdet_view* x, const glsdet_view* y, cons
   a.H = x->h; a.W = x->w; a.C = C;
   a.tokens = (long)x->n * x->h * x->w;
   const int di = x->dtype, dout = y->dtype;
-  OpRecord op;
-  op.kind = 3;
-  op.flops = 8.0 * a.tokens * C;
-  op.bytes = (double)a.tokens * C * (dtype_size(di) + dtype_size(dout)) + 8.0 * C;
-  op.name = "layernorm(two-pass fp32, one wave per token)";
-  op.launch = [=](hipStream_t st) -> int {
-    long g = (a.tokens + 3) / 4;
+  OpRecord op = make_op(3, 8.0 * a.tokens * C, (double)a.tokens * C * (dtype_size(di) + dtype_size(dout)) + 8.0 * C,
+                        "layernorm(two-pass fp32, one wave per token)");
+  return submit_op(std::move(op), stream, [=](hipStream_t st) {
+    long g = (a.tokens + 3) / 4;      // workgroups of 4 tokens, not of 256 items: written out
     if (g > GLS_LN_MAXGRID) g = GLS_LN_MAXGRID;
     const dim3 grid((unsigned)g), block(256);
-    if (di == GLSDET_F16 && dout == GLSDET_F16)
-      hipLaunchKernelGGL((layernorm_kernel<f16, f16>), grid, block, 0, st, a);
-    else if (di == GLSDET_F16)
-      hipLaunchKernelGGL((layernorm_kernel<f16, float>), grid, block, 0, st, a);
-    else if (dout == GLSDET_F16)
-      hipLaunchKernelGGL((layernorm_kernel<float, f16>), grid, block, 0, st, a);
-    else
-      hipLaunchKernelGGL((layernorm_kernel<float, float>), grid, block, 0, st, a);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+    with_dtype(di, [&](auto ti) {
+      with_dtype(dout, [&](auto to) { hipLaunchKernelGGL((layernorm_kernel<decltype(ti), decltype(to)>), grid, block, 0, st, a); });
+    });
+  });
 }
 
 extern "C" int glsdet_patch_merge(const glsdet_view* x, const glsdet_view* y, void* stream) {
-  if (!x || !y) GLS_FAIL(GLSDET_E_ARG, "patch_merge: null argument");
-  int rc;
-  if ((rc = check_view(*x, "patch_merge.x"))) return rc;
-  if ((rc = check_view(*y, "patch_merge.y"))) return rc;
+  if (int rc = check_views("patch_merge: null argument", false, {{x, "patch_merge.x"}, {y, "patch_merge.y"}})) return rc;
   if (x->dtype != y->dtype) GLS_FAIL(GLSDET_E_ARG, "patch_merge: x / y dtypes differ");
   if (views_overlap(*x, *y)) GLS_FAIL(GLSDET_E_ARG, "patch_merge: y overlaps x");
   if (x->c % 8) GLS_FAIL(GLSDET_E_ARG, "patch_merge: channels must be a multiple of 8, got %d", x->c);
@@ -368,32 +339,18 @@ extern "C" int glsdet_patch_merge(const glsdet_view* x, const glsdet_view* y, vo
     GLS_FAIL(GLSDET_E_ARG, "patch_merge: y must be [%d,%d,%d,%ld], got [%d,%d,%d,%d]", x->n, (x->h + 1) / 2, (x->w + 1) / 2,
              4L * x->c, y->n, y->h, y->w, y->c);
   const glsdet_view vx = *x, vy = *y;
-  OpRecord op;
-  op.kind = 3;
-  op.flops = 0;
-  op.bytes = ((double)vx.n * vx.h * vx.w * vx.c + (double)vy.n * vy.h * vy.w * vy.c) * dtype_size(vx.dtype);
-  op.name = "patch_merge(pad + unfold 2x2 / 2)";
-  op.launch = [=](hipStream_t st) -> int {
-    long g = ((long)vy.n * vy.h * vy.w * vx.c + 255) / 256;
-    if (g > 8192) g = 8192;
-    if (vx.dtype == GLSDET_F16)
-      hipLaunchKernelGGL(patch_merge_kernel<f16>, dim3((unsigned)g), dim3(256), 0, st, (const unsigned char*)vx.base, vx.sn, vx.sh,
-                         vx.sw, (unsigned char*)vy.base, vy.sn, vy.sh, vy.sw, vx.n, vx.h, vx.w, vx.c, vy.h, vy.w);
-    else
-      hipLaunchKernelGGL(patch_merge_kernel<float>, dim3((unsigned)g), dim3(256), 0, st, (const unsigned char*)vx.base, vx.sn, vx.sh,
-                         vx.sw, (unsigned char*)vy.base, vy.sn, vy.sh, vy.sw, vx.n, vx.h, vx.w, vx.c, vy.h, vy.w);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  const double bytes = ((double)vx.n * vx.h * vx.w * vx.c + (double)vy.n * vy.h * vy.w * vy.c) * dtype_size(vx.dtype);
+  return submit_op(make_op(3, 0, bytes, "patch_merge(pad + unfold 2x2 / 2)"), stream, [=](hipStream_t st) {
+    const unsigned g = grid_1d((long)vy.n * vy.h * vy.w * vx.c);
+    with_dtype(vx.dtype, [&](auto t) {
+      hipLaunchKernelGGL(patch_merge_kernel<decltype(t)>, dim3(g), dim3(256), 0, st, GLS_VIN(vx), GLS_VOUT(vy), vx.n, vx.h, vx.w, vx.c, vy.h, vy.w);
+    });
+  });
 }
 
 extern "C" int glsdet_window_attention(const glsdet_view* qkv, const glsdet_view* y, const float* bias_table, const float* qkv_bias,
                                        int32_t heads, int32_t ws, int32_t shift, float scale, void* stream) {
-  if (!qkv || !y || !bias_table) GLS_FAIL(GLSDET_E_ARG, "window_attention: null argument");
-  int rc;
-  if ((rc = check_view(*qkv, "window_attention.qkv"))) return rc;
-  if ((rc = check_view(*y, "window_attention.y"))) return rc;
+  if (int rc = check_views("window_attention: null argument", !bias_table, {{qkv, "window_attention.qkv"}, {y, "window_attention.y"}})) return rc;
   if (qkv->dtype != y->dtype) GLS_FAIL(GLSDET_E_ARG, "window_attention: qkv / y dtypes differ");
   const int C = y->c;
   if (C < 32 || C % 32 || C > GLS_WIN_MAXC)
@@ -418,19 +375,10 @@ extern "C" int glsdet_window_attention(const glsdet_view* qkv, const glsdet_view
   a.items = (long)a.n * a.nwh * a.nww * heads;
   const int dt = y->dtype;
   const double N = (double)ws * ws;
-  OpRecord op;
-  op.kind = 4;
-  op.flops = (double)a.items * 4.0 * N * N * 32;
-  op.bytes = (double)a.n * a.H * a.W * 4.0 * C * dtype_size(dt);
-  op.name = "window_attention(qk^T + bias + mask, softmax, pv)";
-  op.launch = [=](hipStream_t st) -> int {
-    const long g = a.items < GLS_WIN_MAXGRID ? a.items : GLS_WIN_MAXGRID;
-    if (dt == GLSDET_F16)
-      hipLaunchKernelGGL(window_attention_kernel<f16>, dim3((unsigned)g), dim3(128), 0, st, a);
-    else
-      hipLaunchKernelGGL(window_attention_kernel<float>, dim3((unsigned)g), dim3(128), 0, st, a);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  OpRecord op = make_op(4, (double)a.items * 4.0 * N * N * 32, (double)a.n * a.H * a.W * 4.0 * C * dtype_size(dt),
+                        "window_attention(qk^T + bias + mask, softmax, pv)");
+  return submit_op(std::move(op), stream, [=](hipStream_t st) {
+    const long g = a.items < GLS_WIN_MAXGRID ? a.items : GLS_WIN_MAXGRID;      // one item per workgroup of 128: written out
+    with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(window_attention_kernel<decltype(t)>, dim3((unsigned)g), dim3(128), 0, st, a); });
+  });
 }

@@ -155,19 +155,9 @@ extern "C" int glsdet_ufp_mosaic(const unsigned char* img, int32_t H, int32_t W,
                                  float* canvas, int32_t ch, int32_t cw, void* stream) {
   if (!img || !canvas || (n_chips > 0 && !chips)) GLS_FAIL(GLSDET_E_ARG, "ufp_mosaic: null argument");
   if (H < 1 || W < 1 || ch < 1 || cw < 1 || n_chips < 0) GLS_FAIL(GLSDET_E_ARG, "ufp_mosaic: bad sizes");
-  OpRecord op;
-  op.kind = 1;
-  op.flops = 0;
-  op.bytes = 12.0 * ch * cw + 3.0 * H * W;
-  op.name = "ufp_mosaic";
-  op.launch = [=](hipStream_t st) -> int {
-    long g = ((long)ch * cw + 255) / 256;
-    if (g > 65535) g = 65535;
-    hipLaunchKernelGGL(ufp_mosaic_kernel, dim3((unsigned)g), dim3(256), 0, st, img, H, W, chips, n_chips, canvas, ch, cw);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  return submit_op(make_op(1, 0, 12.0 * ch * cw + 3.0 * H * W, "ufp_mosaic"), stream, [=](hipStream_t st) {
+    hipLaunchKernelGGL(ufp_mosaic_kernel, dim3(grid_1d((long)ch * cw, 65535)), dim3(256), 0, st, img, H, W, chips, n_chips, canvas, ch, cw);
+  });
 }
 
 extern "C" int glsdet_resize_normalize_pad_ex(const float* src, int32_t h, int32_t w, int32_t nh, int32_t nw, float* dst,
@@ -182,19 +172,9 @@ extern "C" int glsdet_resize_normalize_pad_ex(const float* src, int32_t h, int32
     na.mean[c] = mean_rgb[c];
     na.stdinv[c] = 1.0 / std_rgb[c];
   }
-  OpRecord op;
-  op.kind = 1;
-  op.flops = 0;
-  op.bytes = 12.0 * h * w + 12.0 * ph * pw;
-  op.name = "resize_normalize_pad";
-  op.launch = [=](hipStream_t st) -> int {
-    long g = ((long)ph * pw + 255) / 256;
-    if (g > 65535) g = 65535;
-    hipLaunchKernelGGL(resize_norm_pad_kernel, dim3((unsigned)g), dim3(256), 0, st, src, h, w, nh, nw, dst, ph, pw, na, flip);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  return submit_op(make_op(1, 0, 12.0 * h * w + 12.0 * ph * pw, "resize_normalize_pad"), stream, [=](hipStream_t st) {
+    hipLaunchKernelGGL(resize_norm_pad_kernel, dim3(grid_1d((long)ph * pw, 65535)), dim3(256), 0, st, src, h, w, nh, nw, dst, ph, pw, na, flip);
+  });
 }
 
 extern "C" int glsdet_resize_normalize_pad(const float* src, int32_t h, int32_t w, int32_t nh, int32_t nw, float* dst,
@@ -215,19 +195,9 @@ extern "C" int glsdet_resize_normalize_pad_u8_ex(const unsigned char* src, int32
     na.mean[c] = mean_rgb[c];
     na.stdinv[c] = 1.0 / std_rgb[c];
   }
-  OpRecord op;
-  op.kind = 1;
-  op.flops = 0;
-  op.bytes = 3.0 * h * w + 12.0 * ph * pw;
-  op.name = "resize_normalize_pad_u8";
-  op.launch = [=](hipStream_t st) -> int {
-    long g = ((long)ph * pw + 255) / 256;
-    if (g > 65535) g = 65535;
-    hipLaunchKernelGGL(resize_norm_pad_u8_kernel, dim3((unsigned)g), dim3(256), 0, st, src, h, w, nh, nw, dst, ph, pw, na, flip);
-    GLS_HIP(hipGetLastError());
-    return 0;
-  };
-  return submit(std::move(op), stream);
+  return submit_op(make_op(1, 0, 3.0 * h * w + 12.0 * ph * pw, "resize_normalize_pad_u8"), stream, [=](hipStream_t st) {
+    hipLaunchKernelGGL(resize_norm_pad_u8_kernel, dim3(grid_1d((long)ph * pw, 65535)), dim3(256), 0, st, src, h, w, nh, nw, dst, ph, pw, na, flip);
+  });
 }
 
 extern "C" int glsdet_resize_normalize_pad_u8(const unsigned char* src, int32_t h, int32_t w, int32_t nh, int32_t nw,

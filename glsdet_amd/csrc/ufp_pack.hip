@@ -373,11 +373,7 @@ extern "C" int glsdet_ufp_pack(const float* dets, const int32_t* count, int32_t 
   a.dets = dets; a.count = count; a.chips = chips; a.chips_floor = chips_floor; a.header = header; a.status = status;
   a.max_det = max_det; a.img_w = img_w; a.img_h = img_h; a.expand = expand;
   const int lds = UFPK_ROW * max_det + UFPK_TAIL;
-  OpRecord op;
-  op.kind = 6;
-  op.flops = 0;
-  op.bytes = (double)n_img * max_det * (28.0 + 84.0);
-  op.name = "ufp_pack";
+  OpRecord op = make_op(6, 0, (double)n_img * max_det * (28.0 + 84.0), "ufp_pack");
   op.launch = [=](hipStream_t st) -> int {
     static int attr_lds = 64 * 1024;
     if (lds > attr_lds) {

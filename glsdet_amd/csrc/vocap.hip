@@ -333,11 +333,7 @@ extern "C" int glsdet_voc_ap(const double* dt_box, const double* score, const in
   a.ND = n_dt; a.C = n_cls; a.P = n_pairs; a.NG = n_gt_boxes; a.T = n_thr;
   a.used = (unsigned char*)wsp;
   a.tp = tp; a.fp = fp; a.rec = rec; a.prec = prec; a.mpre = mpre; a.cls_out = cls_out;
-  OpRecord op;
-  op.kind = 6;
-  op.flops = 0;
-  op.bytes = 44.0 * n_dt + 33.0 * n_gt_boxes + (double)n_thr * (32.0 * n_dt + n_gt_boxes);
-  op.name = "voc_ap(match+curve)";
+  OpRecord op = make_op(6, 0, 44.0 * n_dt + 33.0 * n_gt_boxes + (double)n_thr * (32.0 * n_dt + n_gt_boxes), "voc_ap(match+curve)");
   op.launch = [=](hipStream_t st) -> int {
     const long nm = (long)a.P * a.T;
     if (nm > 0) {
