@@ -9,7 +9,7 @@
 //
 // voc_match_kernel: one wave per ((class, image) pair, threshold), lanes across the pair's ground truths, the pair's
 // detections sequential in rank order (a match consumes a ground truth).  The `used` flags live in the workspace (no cap
-// on the ground truths of a pair); they are cleared by a memset ahead of the kernel and then read and written by lane 0
+// on the ground truths of a pair); they are cleared by voc_reset_used_kernel ahead of the kernel and then read and written by lane 0
 // alone, so no lane ever reads what another lane of the wave stored and the kernel needs no wave-level fence.
 // voc_curve_kernel: one workgroup per (class, threshold): chunked scans with a carry, then the sequential AP sum over the
 // compacted change points of the recall (at most tp + 1 terms).
@@ -21,6 +21,7 @@ namespace glsdet {
 // grid caps; the kernels stride over what is left
 constexpr long VOC_MATCH_GRID = 16384;    // waves: (pair, threshold)
 constexpr long VOC_CURVE_GRID = 512;      // workgroups: (class, threshold)
+constexpr long VOC_RESET_GRID = 1024;     // workgroups of 256 flags, grid-stride beyond
 
 struct VocArgs {
   const double* dt_box;      // [ND][4] left, top, right, bottom; class-major, rank order inside a class
@@ -58,6 +59,13 @@ __device__ __forceinline__ void wave_argmax_first(double& v, int& pos) {
       pos = op;
     }
   }
+}
+
+// The `used` flags are cleared by a kernel of the op's own, not by hipMemsetAsync: replayed from a captured graph the memset
+// node did not clear them (tests/test_replay_invariance.py: eager replay equal to the immediate launch, graph replay not),
+// the observation csrc/post.hip records for its counters.
+__global__ __launch_bounds__(256) void voc_reset_used_kernel(unsigned char* used, long n) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) used[i] = 0;
 }
 
 __global__ __launch_bounds__(64) void voc_match_kernel(VocArgs a) {
@@ -337,7 +345,10 @@ extern "C" int glsdet_voc_ap(const double* dt_box, const double* score, const in
   op.launch = [=](hipStream_t st) -> int {
     const long nm = (long)a.P * a.T;
     if (nm > 0) {
-      if (a.NG > 0) GLS_HIP(hipMemsetAsync(a.used, 0, (size_t)a.NG * (size_t)a.T, st));
+      const long nu = (long)a.NG * a.T, nb = (nu + 255) / 256;
+      if (nu > 0)
+        hipLaunchKernelGGL(voc_reset_used_kernel, dim3((unsigned)(nb < VOC_RESET_GRID ? nb : VOC_RESET_GRID)), dim3(256), 0, st,
+                           a.used, nu);
       hipLaunchKernelGGL(voc_match_kernel, dim3((unsigned)(nm < VOC_MATCH_GRID ? nm : VOC_MATCH_GRID)), dim3(64), 0, st, a);
     }
     const long nc = (long)a.C * a.T;
